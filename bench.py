@@ -22,6 +22,14 @@ Defaults (no flags): N=1, steps=60, warmup=5 — ~2 s of measured flagship
 work on one MI355X, long enough for the driver's rocm-smi utilisation
 sampler to catch >=2 samples (VERDICT r1 hygiene item).
 
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps update steps, print the result line. --dump-outputs DIR also
+writes what the last timed step returned (metrics and the updated
+parameters) as DIR/<name>.npy; seeds are fixed, so two builds given the
+same arguments start from identical inputs and can be compared array for
+array. --full is where measurements beyond the headline figure belong;
+none exist today, so it changes nothing yet.
+
 Launch (multi-GPU, by the driver):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
@@ -251,6 +259,44 @@ BUILDERS = {
 }
 
 
+# ---------------------------------------------------------- output dump
+
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, learner, metrics) -> None:
+    """Write what the last timed update_step handed back — its metrics dict
+    and the parameters it left in the learner — as <out_dir>/<name>.npy
+    (float32; float64 tensors stay float64). The total stays under
+    DUMP_BUDGET_BYTES: an array over its even share of the budget is
+    replaced by a fixed seeded sample of its flattened elements."""
+    import numpy as np
+
+    arrays = {}
+    for k, v in (metrics or {}).items():
+        arrays[f"metrics.{k}"] = v
+    for net, sd in learner.state_for_checkpoint().items():
+        if torch.is_tensor(sd):  # a bare tensor entry, e.g. SAC's log_alpha
+            arrays[f"params.{net}"] = sd
+            continue
+        for k, v in sd.items():
+            if torch.is_tensor(v):
+                arrays[f"params.{net}.{k}"] = v
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        a = t.numpy()
+        if a.nbytes > share:
+            # same seed for every array: equal-sized arrays share one index
+            # set (harmless). choice() permutes all a.size indices, which is
+            # fine for network-sized arrays.
+            idx = np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 # ------------------------------------------------------------------ main
 
 
@@ -334,7 +380,16 @@ def main() -> None:
     p.add_argument("--env", type=str, default="brax/ant")
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-graph", action="store_true", help="disable hip-graph capture")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned "
+                        "(metrics + updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure; a plain run "
+                        "already times only the selected config, so today this adds none")
     args = p.parse_args()
+    if args.dump_outputs and args.config == "sebulba":
+        p.error("--dump-outputs is not supported with --config sebulba "
+                "(asynchronous actor threads: no deterministic last step)")
 
     import torch.distributed as dist
 
@@ -416,11 +471,15 @@ def main() -> None:
         learner.update_step()
     barrier_sync()
 
+    metrics = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        learner.update_step()
+        metrics = learner.update_step()
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and ctx.is_main:
+        dump_outputs(args.dump_outputs, learner, metrics)
 
     # max over ranks
     if ctx.initialized:

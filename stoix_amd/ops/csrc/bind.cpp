@@ -38,7 +38,7 @@ void launch_fused_adam(float*, const float*, float*, float*, float*, long*,
                        long, float, float, float, float, float, void*);
 void launch_fused_adam_bf16(float*, const void*, float*, float*, float*,
                             long*, void*, long, float, float, float, float,
-                            float, float, int, void*);
+                            float, float, int, long, void*);
 void launch_polyak(const float*, float*, long, float, void*);
 void launch_mfma_probe(const void*, const void*, float*, float*, void*);
 void launch_policy_value_step(const float*, const void*, const float*,
@@ -281,7 +281,8 @@ void fused_adam_bf16(torch::Tensor param, torch::Tensor grad,
                          sqnorm.data_ptr<float>(), step_t.data_ptr<long>(),
                          pbf, param.numel(), (float)lr, (float)beta1,
                          (float)beta2, (float)eps, (float)max_norm,
-                         (float)grad_scale, (int)do_prologue, cur_stream());
+                         (float)grad_scale, (int)do_prologue,
+                         (long)sqnorm.numel(), cur_stream());
 }
 
 void mfma_probe(torch::Tensor A, torch::Tensor B, torch::Tensor D0,

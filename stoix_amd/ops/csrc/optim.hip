@@ -86,8 +86,14 @@ extern "C" __global__ void adam_prologue_kernel(float* __restrict__ sqnorm,
 typedef __bf16 opt_bf16;
 typedef __bf16 opt_bf16x8 __attribute__((ext_vector_type(8)));
 
+// `partials` non-null: block b stores its sum in partials[b] and
+// adam_update_bf16_kernel adds them up in index order, so the norm (hence
+// the clip factor and every clipped update) is bit-reproducible run to run.
+// Null: one float atomicAdd per block into *out (order varies in the last
+// bits).
 extern "C" __global__ void grad_sqnorm_bf16_kernel(
-    const opt_bf16* __restrict__ grad, float* __restrict__ out, long n) {
+    const opt_bf16* __restrict__ grad, float* __restrict__ out,
+    float* __restrict__ partials, long n) {
   long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
   float acc = 0.0f;
@@ -116,21 +122,48 @@ extern "C" __global__ void grad_sqnorm_bf16_kernel(
     float s = 0.0f;
     int nw = (blockDim.x + 63) / 64;
     for (int w = 0; w < nw; ++w) s += warp_sums[w];
-    atomicAdd(out, s);
+    if (partials)
+      partials[blockIdx.x] = s;
+    else
+      atomicAdd(out, s);
   }
 }
 
+// n_partials > 0: sqnorm[1 .. n_partials] hold grad_sqnorm_bf16_kernel's
+// per-block sums; every block adds them in the same fixed order (wave 0:
+// lane-strided, then the shuffle tree) and block 0 stores the total in
+// sqnorm[0]. n_partials == 0: sqnorm[0] already holds the atomic total.
 extern "C" __global__ void adam_update_bf16_kernel(
     float* __restrict__ param, const opt_bf16* __restrict__ grad,
     float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-    const float* __restrict__ sqnorm, const long* __restrict__ step_t,
+    float* __restrict__ sqnorm, const long* __restrict__ step_t,
     opt_bf16* __restrict__ param_bf16, long n, float lr, float beta1,
-    float beta2, float eps, float max_norm, float grad_scale) {
+    float beta2, float eps, float max_norm, float grad_scale,
+    int n_partials) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
   float clip = grad_scale;
   if (max_norm > 0.0f) {
-    float norm = sqrtf(*sqnorm) * grad_scale;
+    float sq;
+    if (n_partials > 0) {
+      __shared__ float total;
+      if (threadIdx.x < 64) {
+        float acc = 0.0f;
+        for (int p = threadIdx.x; p < n_partials; p += 64)
+          acc += sqnorm[1 + p];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+        if (threadIdx.x == 0) {
+          total = acc;
+          if (blockIdx.x == 0) sqnorm[0] = acc;
+        }
+      }
+      __syncthreads();
+      sq = total;
+    } else {
+      sq = *sqnorm;
+    }
+    float norm = sqrtf(sq) * grad_scale;
     if (norm > max_norm) clip = grad_scale * max_norm / (norm + 1e-6f);
   }
   long t = *step_t;
@@ -152,7 +185,11 @@ extern "C" void launch_fused_adam_bf16(float* param, const void* grad,
                                        void* param_bf16, long n, float lr,
                                        float beta1, float beta2, float eps,
                                        float max_norm, float grad_scale,
-                                       int do_prologue, void* stream) {
+                                       int do_prologue, long sqnorm_len,
+                                       void* stream) {
+  // sqnorm_len: floats in the sqnorm buffer. With room for one partial per
+  // block behind sqnorm[0] the norm is summed in a fixed order
+  // (reproducible); a 1-element buffer keeps the atomic form.
   hipStream_t s = (hipStream_t)stream;
   // the prologue (zero sqnorm, step+1) can ride along in slab_reduce
   // (wgrad.hip) when that kernel precedes this one in the same stream
@@ -162,16 +199,20 @@ extern "C" void launch_fused_adam_bf16(float* param, const void* grad,
   int threads = 256;
   long want = (n / 8 + threads - 1) / threads;
   int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
+  int n_partials = 0;
   if (max_norm > 0.0f) {
+    bool ordered = sqnorm_len >= 1 + (long)blocks;
+    if (ordered) n_partials = blocks;
     hipLaunchKernelGGL(grad_sqnorm_bf16_kernel, dim3(blocks), dim3(threads),
-                       0, s, (const opt_bf16*)grad, sqnorm, n);
+                       0, s, (const opt_bf16*)grad, sqnorm,
+                       ordered ? sqnorm + 1 : (float*)nullptr, n);
   }
   long want2 = (n + threads - 1) / threads;
   int blocks2 = (int)(want2 < 2048 ? (want2 > 0 ? want2 : 1) : 2048);
   hipLaunchKernelGGL(adam_update_bf16_kernel, dim3(blocks2), dim3(threads), 0,
                      s, param, (const opt_bf16*)grad, exp_avg, exp_avg_sq,
                      sqnorm, step_t, (opt_bf16*)param_bf16, n, lr, beta1,
-                     beta2, eps, max_norm, grad_scale);
+                     beta2, eps, max_norm, grad_scale, n_partials);
 }
 
 // polyak: target <- tau * online + (1 - tau) * target (ff_dqn.py:207-209)

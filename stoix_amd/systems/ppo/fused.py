@@ -111,7 +111,10 @@ class _Chain:
         )
         self.m = torch.zeros(total, dtype=torch.float32, device=device)
         self.v = torch.zeros(total, dtype=torch.float32, device=device)
-        self.sqnorm = torch.zeros(1, dtype=torch.float32, device=device)
+        # [0] = squared grad norm; [1:] = room for one partial sum per block
+        # of the norm kernel (<= 2048 blocks), which fused_adam_bf16 then
+        # adds in a fixed order: bit-reproducible clipping run to run
+        self.sqnorm = torch.zeros(1 + 2048, dtype=torch.float32, device=device)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=device)
         self.views: Dict[str, Tensor] = {}
         self.views16: Dict[str, Tensor] = {}

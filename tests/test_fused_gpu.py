@@ -261,6 +261,64 @@ def test_fused_adam_bf16_matches_torch(ext):
 
 
 @requires_gpu
+def test_fused_adam_bf16_ordered_norm_is_reproducible(ext):
+    """With room for per-block partials behind sqnorm[0], the grad norm is
+    summed in a fixed order: two runs from the same state are bit-identical,
+    exactly the 49 partial slots this size needs are written, sqnorm[0] is
+    their sum in the kernel's order (lane-strided, then the shuffle tree),
+    and the update still matches torch clip+Adam. n spans 49 norm blocks
+    with a tail that is no multiple of the 8-wide vector."""
+    n = 100_003
+    g = torch.Generator().manual_seed(7)
+    p0 = torch.randn(n, generator=g).cuda()
+    grads = [torch.randn(n, generator=g).cuda().bfloat16() for _ in range(3)]
+    lr, max_norm = 3e-4, 0.5
+
+    def run():
+        p32 = p0.clone()
+        m = torch.zeros(n).cuda()
+        v = torch.zeros(n).cuda()
+        sqn = torch.zeros(1 + 2048).cuda()
+        st = torch.zeros(1, dtype=torch.int64).cuda()
+        p16 = torch.zeros(n, dtype=torch.bfloat16).cuda()
+        for g16 in grads:
+            ext.fused_adam_bf16(p32, g16, m, v, sqn, st, p16, lr, 0.9, 0.999,
+                                1e-5, max_norm, 1.0, 1)
+        torch.cuda.synchronize()
+        return p32, sqn
+
+    pa, sqa = run()
+    pb, sqb = run()
+    assert torch.equal(pa, pb)
+    assert torch.equal(sqa, sqb)
+    # the ordered path ran (not the atomic fallback): one partial per block,
+    # blocks = ceil((n // 8) / 256) = 49, nothing written past them
+    blocks = (n // 8 + 255) // 256
+    assert blocks == 49
+    parts = sqa[1 : 1 + blocks].cpu()
+    assert (parts > 0).all()
+    assert (sqa[1 + blocks :] == 0).all()
+    # replay the kernel's order in fp32: lane l takes partials l, l+64, ...
+    # (at most one here), then acc[l] += acc[l + off] for off = 32 .. 1
+    lanes = torch.zeros(64)
+    lanes[:blocks] = parts
+    for off in (32, 16, 8, 4, 2, 1):
+        lanes[:off] = lanes[:off] + lanes[off : 2 * off]
+    assert torch.equal(lanes[0], sqa[0].cpu())
+    # fp32 sum of 1e5 squares in short chains + trees: well inside 1e-5
+    want = grads[-1].double().pow(2).sum()
+    torch.testing.assert_close(sqa[0].double(), want, rtol=1e-5, atol=0.0)
+
+    ref_p = torch.nn.Parameter(p0.clone())
+    opt = torch.optim.Adam([ref_p], lr=lr, eps=1e-5)
+    for g16 in grads:
+        ref_p.grad = g16.float()
+        torch.nn.utils.clip_grad_norm_([ref_p], max_norm)
+        opt.step()
+    torch.testing.assert_close(pa, ref_p.detach(), rtol=1e-4, atol=1e-5)
+
+
+@requires_gpu
 def test_fused_ppo_update_step_runs_and_learns_shape(ext):
     """End-to-end: PPOLearner with the fused engine active — one update
     step runs, metrics finite, and the fused path is actually attached."""
