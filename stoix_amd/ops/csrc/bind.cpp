@@ -296,6 +296,53 @@ const float* fptr_or_null(const torch::Tensor& t) {
   return t.numel() > 0 ? t.data_ptr<float>() : nullptr;
 }
 
+unsigned int* draw_or_null(const torch::Tensor& draw_buf) {
+  return draw_buf.numel() > 0 ? (unsigned int*)draw_buf.data_ptr<int>()
+                              : nullptr;
+}
+
+// A fused-MLP weight (mlp.hip): contiguous bf16 on the GPU, `rows` x `cols`.
+void check_fused_weight(const torch::Tensor& w, const char* name,
+                        int64_t rows, int64_t cols) {
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                  w.scalar_type() == torch::kBFloat16,
+              name, " must be a contiguous bf16 GPU tensor");
+  TORCH_CHECK(w.numel() == rows * cols && w.size(0) == rows, name,
+              " must be [", rows, ", ", cols, "]");
+}
+
+// Argument checks shared by the fused-MLP wrappers (mlp.hip). The kernels
+// exist for HID 128/256/512 only (HID = rows of the critic's W2), stage at
+// most 128 obs columns and read W1 with the obs width padded to the MFMA
+// K-step. Returns HID.
+int check_fused_mlp(const torch::Tensor& obs, const torch::Tensor& W1c,
+                    const torch::Tensor& W2c, const torch::Tensor& Wvc) {
+  CHK(obs, torch::kFloat32);
+  const int64_t HID = W2c.size(0), OBS = obs.size(1);
+  TORCH_CHECK(HID == 512 || HID == 256 || HID == 128,
+              "fused MLP supports HID 128/256/512, got ", HID);
+  TORCH_CHECK(OBS <= 128, "fused MLP supports OBS <= 128, got ", OBS);
+  check_fused_weight(W1c, "W1c", HID, (OBS + 31) & ~31);
+  check_fused_weight(W2c, "W2c", HID, HID);
+  check_fused_weight(Wvc.view({-1, 1}), "Wvc", HID, 1);
+  return (int)HID;
+}
+
+// The same with an actor of the same width, whose head is one 16-column
+// tile holding at most `act_max` actions (8 tanh-normal dims or 16 logits).
+int check_fused_mlp(const torch::Tensor& obs, const torch::Tensor& W1a,
+                    const torch::Tensor& W2a, const torch::Tensor& Wha,
+                    const torch::Tensor& W1c, const torch::Tensor& W2c,
+                    const torch::Tensor& Wvc, int64_t ACT, int64_t act_max) {
+  const int HID = check_fused_mlp(obs, W1c, W2c, Wvc);
+  check_fused_weight(W1a, "W1a", HID, W1c.size(1));
+  check_fused_weight(W2a, "W2a", HID, HID);
+  check_fused_weight(Wha, "Wha", 16, HID);
+  TORCH_CHECK(ACT <= act_max, "fused policy head supports ACT <= ", act_max,
+              ", got ", ACT);
+  return HID;
+}
+
 void policy_value_step(torch::Tensor obs, torch::Tensor W1a, torch::Tensor b1a,
                        torch::Tensor W2a, torch::Tensor b2a, torch::Tensor Wha,
                        torch::Tensor bha, torch::Tensor W1c, torch::Tensor b1c,
@@ -307,20 +354,10 @@ void policy_value_step(torch::Tensor obs, torch::Tensor W1a, torch::Tensor b1a,
                        double aff_shift, double log_aff_scale, int64_t greedy,
                        int64_t seed, torch::Tensor draw_buf,
                        int64_t draw_offset, int64_t do_bump) {
-  CHK(obs, torch::kFloat32);
-  CHK(W1a, torch::kBFloat16);
-  CHK(W2a, torch::kBFloat16);
   int B = obs.size(0), OBS = obs.size(1);
-  int HID = W2a.size(0);
   int ACT = action_out.size(1);
-  TORCH_CHECK(HID == 512 || HID == 256 || HID == 128,
-              "fused MLP supports HID 128/256/512");
-  TORCH_CHECK(ACT <= 8, "fused policy head supports ACT <= 8");
-  TORCH_CHECK(OBS <= 128, "fused MLP supports OBS <= 128");
+  int HID = check_fused_mlp(obs, W1a, W2a, Wha, W1c, W2c, Wvc, ACT, 8);
   float* om = obs_mirror.numel() > 0 ? obs_mirror.data_ptr<float>() : nullptr;
-  unsigned int* db = draw_buf.numel() > 0
-                         ? (unsigned int*)draw_buf.data_ptr<int>()
-                         : nullptr;
   launch_policy_value_step(
       obs.data_ptr<float>(), W1a.data_ptr(), b1a.data_ptr<float>(),
       W2a.data_ptr(), b2a.data_ptr<float>(), Wha.data_ptr(),
@@ -330,8 +367,9 @@ void policy_value_step(torch::Tensor obs, torch::Tensor W1a, torch::Tensor b1a,
       logp_out.data_ptr<float>(), value_out.data_ptr<float>(),
       fptr_or_null(nmean), fptr_or_null(nvar), B, OBS, ACT, HID,
       (float)min_scale, (float)aff_scale, (float)aff_shift,
-      (float)log_aff_scale, (int)greedy, (uint64_t)seed, db,
-      (unsigned int)draw_offset, (int)do_bump, cur_stream());
+      (float)log_aff_scale, (int)greedy, (uint64_t)seed,
+      draw_or_null(draw_buf), (unsigned int)draw_offset, (int)do_bump,
+      cur_stream());
 }
 
 void policy_value_step_disc(
@@ -343,20 +381,11 @@ void policy_value_step_disc(
     torch::Tensor logp_out, torch::Tensor value_out, torch::Tensor nmean,
     torch::Tensor nvar, int64_t num_actions, int64_t greedy, int64_t seed,
     torch::Tensor draw_buf, int64_t draw_offset, int64_t do_bump) {
-  CHK(obs, torch::kFloat32);
-  CHK(W1a, torch::kBFloat16);
   CHK(action_out, torch::kInt64);
   int B = obs.size(0), OBS = obs.size(1);
-  int HID = W2a.size(0);
   int ACT = (int)num_actions;
-  TORCH_CHECK(HID == 512 || HID == 256 || HID == 128,
-              "fused MLP supports HID 128/256/512");
-  TORCH_CHECK(ACT <= 16, "fused categorical head supports ACT <= 16");
-  TORCH_CHECK(OBS <= 128, "fused MLP supports OBS <= 128");
+  int HID = check_fused_mlp(obs, W1a, W2a, Wha, W1c, W2c, Wvc, ACT, 16);
   float* om = obs_mirror.numel() > 0 ? obs_mirror.data_ptr<float>() : nullptr;
-  unsigned int* db = draw_buf.numel() > 0
-                         ? (unsigned int*)draw_buf.data_ptr<int>()
-                         : nullptr;
   launch_policy_value_step_disc(
       obs.data_ptr<float>(), W1a.data_ptr(), b1a.data_ptr<float>(),
       W2a.data_ptr(), b2a.data_ptr<float>(), Wha.data_ptr(),
@@ -365,8 +394,8 @@ void policy_value_step_disc(
       bvc.data_ptr<float>(), om, action_out.data_ptr<long>(),
       logp_out.data_ptr<float>(), value_out.data_ptr<float>(),
       fptr_or_null(nmean), fptr_or_null(nvar), B, OBS, ACT, HID, (int)greedy,
-      (uint64_t)seed, db, (unsigned int)draw_offset, (int)do_bump,
-      cur_stream());
+      (uint64_t)seed, draw_or_null(draw_buf), (unsigned int)draw_offset,
+      (int)do_bump, cur_stream());
 }
 
 void ppo_head_loss_disc(torch::Tensor heads, torch::Tensor v_in,
@@ -417,10 +446,8 @@ void value_forward(torch::Tensor obs, torch::Tensor W1c, torch::Tensor b1c,
                    torch::Tensor W2c, torch::Tensor b2c, torch::Tensor Wvc,
                    torch::Tensor bvc, torch::Tensor value_out,
                    torch::Tensor nmean, torch::Tensor nvar) {
-  CHK(obs, torch::kFloat32);
-  CHK(W1c, torch::kBFloat16);
   int B = obs.size(0), OBS = obs.size(1);
-  int HID = W2c.size(0);
+  int HID = check_fused_mlp(obs, W1c, W2c, Wvc);
   launch_value_forward(obs.data_ptr<float>(), W1c.data_ptr(),
                        b1c.data_ptr<float>(), W2c.data_ptr(),
                        b2c.data_ptr<float>(), Wvc.data_ptr(),
@@ -446,11 +473,14 @@ void rollout_step_ant(torch::Tensor obs_io, torch::Tensor env_state,
                       double log_aff_scale, int64_t policy_seed,
                       int64_t env_seed, torch::Tensor policy_draw,
                       torch::Tensor env_draw, int64_t draw_offset) {
-  CHK(obs_io, torch::kFloat32);
   CHK(env_state, torch::kFloat32);
-  CHK(W1a, torch::kBFloat16);
-  int B = obs_io.size(0), OBS = obs_io.size(1);
-  int HID = W2a.size(0), ACT = buf_action.size(1);
+  int B = obs_io.size(0), OBS = obs_io.size(1), ACT = buf_action.size(1);
+  int HID =
+      check_fused_mlp(obs_io, W1a, W2a, Wha, W1c, W2c, Wvc, ACT, 8);
+  // the megakernel hard-codes the Ant's shapes (ant_core.h)
+  TORCH_CHECK(OBS == 27 && ACT == 8,
+              "rollout_step_ant needs OBS == 27 and ACT == 8, got ", OBS,
+              " and ", ACT);
   launch_rollout_step_ant(
       obs_io.data_ptr<float>(), env_state.data_ptr<float>(),
       step_count.data_ptr<int>(), ep_return.data_ptr<float>(),
@@ -534,9 +564,6 @@ void ppo_head_loss(torch::Tensor heads, torch::Tensor v_in,
   CHK(action, torch::kFloat32);
   int B = heads.size(0), ACT = action.size(1);
   TORCH_CHECK(heads.size(1) == 16, "heads must be [B,16] (loc|scale packed)");
-  unsigned int* db = draw_buf.numel() > 0
-                         ? (unsigned int*)draw_buf.data_ptr<int>()
-                         : nullptr;
   void* dv16p = dv16.numel() > 0 ? dv16.data_ptr() : nullptr;
   float* mp = metrics.numel() > 0 ? metrics.data_ptr<float>() : nullptr;
   launch_ppo_head_loss(
@@ -546,8 +573,9 @@ void ppo_head_loss(torch::Tensor heads, torch::Tensor v_in,
       dv.data_ptr(), dv16p, mp, B, ACT,
       (float)clip_eps,
       (float)ent_coef, (float)vf_coef, (float)min_scale, (float)aff_scale,
-      (float)aff_shift, (float)log_aff_scale, (uint64_t)seed, db,
-      (unsigned int)draw_offset, (int)do_bump, cur_stream());
+      (float)aff_shift, (float)log_aff_scale, (uint64_t)seed,
+      draw_or_null(draw_buf), (unsigned int)draw_offset, (int)do_bump,
+      cur_stream());
 }
 
 void wgrad(torch::Tensor dZ, torch::Tensor X, torch::Tensor slab,

@@ -1,29 +1,47 @@
 // Fused MLP kernels for the Anakin hot path (K2/K3/K6/K7 of SURVEY.md §2.9).
 //
 // The reference's XLA fuses scan(env.step ∘ net.apply) into few kernels
-// (/root/reference/stoix/systems/ppo/anakin/ff_ppo.py:118-146); the eager
-// PyTorch equivalent issues ~45 kernels per rollout step. These kernels
-// collapse the canonical actor/critic MLP (obs -> Linear(H) -> SiLU ->
-// Linear(H) -> SiLU -> heads) into:
-//   * policy_value_step_kernel: ONE launch for actor fwd + tanh-normal
-//     sample + log-prob + critic fwd over the whole env batch, using
-//     v_mfma_f32_16x16x32_bf16 matrix cores with LDS-staged activations;
+// (stoix/systems/ppo/anakin/ff_ppo.py:118-146); the eager PyTorch
+// equivalent issues ~45 kernels per rollout step. These kernels collapse
+// the canonical actor/critic MLP (obs -> Linear(H) -> SiLU -> Linear(H) ->
+// SiLU -> heads) into:
+//   * policy_value_step_kernel / policy_value_step_disc_kernel: ONE launch
+//     for actor fwd + sample + log-prob + critic fwd over the whole env
+//     batch (tanh-normal / categorical head);
+//   * rollout_step_ant_kernel: that step plus the Ant physics, autoreset
+//     and the bootstrap critic in the same launch (megakernel);
 //   * value_forward_kernel: critic-only fwd (bootstrap values / eval);
-//   * ppo_fused_head_loss_kernel: per-row head forward + PPO losses +
-//     analytic head backward for the update phase (one wave per sample);
-//   * silu fwd/bwd + gather kernels: the epilogue/prologue glue so the
-//     update phase is GEMM (hipBLASLt MFMA) + a handful of fused kernels.
+//   * ppo_head_loss_kernel / ppo_head_loss_disc_kernel: per-row head
+//     losses + analytic head backward for the update phase (one thread
+//     per sample row);
+//   * linear_silu, silu fwd/bwd + gather kernels: the epilogue/prologue
+//     glue so the update phase is GEMM (hipBLASLt MFMA) + a handful of
+//     fused kernels.
 //
-// Geometry (policy/value forward): one workgroup = 4 waves = 64 batch rows;
-// each wave owns a 16-row M-tile and computes every 16-col N-tile of each
-// layer with mfma_f32_16x16x32_bf16, staging activations in LDS (row-major,
-// +8 col pad -> conflict-free ds_read_b128 A-fragments, §2 of the CDNA4
-// guide). Weights are read straight from L2 (nn.Linear row-major [N,K]
-// bf16 mirrors; they are hot across the 128 sequential rollout steps).
-// Per-wave row blocks are private, so the kernels need NO __syncthreads().
+// Geometry (forward kernels): one workgroup of 4 waves owns ONE 16-row
+// batch tile. Each layer's N (HID columns) is split across the waves: wave
+// w computes N-tiles [w*NTW, (w+1)*NTW) with v_mfma_f32_16x16x32_bf16.
+// Activations ping/pong between LDS tiles (row-major bf16, +8 col pad ->
+// conflict-free ds_read_b128 A-fragments, §2 of the CDNA4 guide); every
+// wave reads the whole previous layer, so a __syncthreads() sits between
+// dependent layers. Weights are read straight from L2 (nn.Linear row-major
+// [N,K] bf16 mirrors; they are hot across the 128 sequential rollout
+// steps). The heads run on single waves after the torso: the critic dot
+// product on wave 1 (wave 0 in critic-only passes), the 16-column actor
+// head tile on wave 0.
+//
+// The three step kernels share one forward (actor_critic_forward, whose
+// call sequence the megakernel spells out for its register allocation, +
+// head_tile) and, for the tanh-normal head, one sampling epilogue
+// (tanh_normal_sample). HID is a template parameter; dispatch_hid maps the
+// runtime width onto the same instantiations {128, 256, 512} of every
+// templated kernel.
 #include "common.h"
 #include "ant_core.h"
 #include <hip/hip_bf16.h>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -99,9 +117,6 @@ extern "C" __global__ void mfma_probe_kernel(const bf16_t* __restrict__ A,
 
 // ------------------------------------------------- fused policy/value fwd
 //
-// LDS: one __shared__ array (guide §5.5 trap 4a), two regions per wave:
-//   O: obs tile      [4 waves][16 rows][K1P<=128 + 8 pad] bf16
-//   H: activations   [4 waves][16 rows][HID + 8 pad]      bf16
 // A-fragment read (ds_read_b128): lane l -> row l&15, k0=(l>>4)*8.
 // B-fragment read (global, row-major [N,K] bf16): lane l -> n=nt*16+(l&15),
 // k0=ks*32+(l>>4)*8 -> 16B contiguous in K.
@@ -112,17 +127,21 @@ extern "C" __global__ void mfma_probe_kernel(const bf16_t* __restrict__ A,
 
 // One workgroup = 4 waves sharing ONE 16-row M-tile; each wave owns NT/4
 // of the N-tiles per layer (split-N). 4096 envs -> 256 workgroups -> every
-// CU busy (the old 64-row-per-WG layout filled only 64 of 256 CUs).
-// Buffers: obs tile + per-net ping/pong activation tiles (actor 0/1,
-// critic 2/3) in ONE __shared__ struct (guide §5.5 trap 4a).
+// CU busy. Buffers: obs tile + per-net ping/pong activation tiles (actor
+// 0/1, critic 2/3) in ONE __shared__ struct (guide §5.5 trap 4a).
 template <int HID>
 struct MlpLds {
-  bf16_t O[16][K1P_MAX + OPAD];
-  bf16_t H[4][16][HID + HPAD];
+  static constexpr int OS = K1P_MAX + OPAD;  // obs tile row stride
+  static constexpr int HS = HID + HPAD;      // activation tile row stride
+  bf16_t O[16][OS];
+  bf16_t H[4][16][HS];
   float act[16][8];  // sampled actions for the in-kernel env step
   int done[16];      // per-row episode-end flags from the env phase
   int any_done;      // OR of done[] (gates the bootstrap critic pass)
 };
+
+// OBS padded to the MFMA K-step (the row stride of the W1 mirrors).
+DEV_INLINE int k1_padded(int OBS) { return (OBS + 31) & ~31; }
 
 // Load one B fragment from a row-major [N,K] bf16 weight matrix.
 template <int HID>
@@ -176,10 +195,17 @@ DEV_INLINE void wg_layer(const bf16_t* __restrict__ src, int sstride,
   }
 }
 
-// Stage one wave's 16 obs rows into LDS as bf16 (zero-padded to K1P), with
-// optional Welford normalisation (mean/var fp32, reference
-// running_statistics.py:205-...); optionally mirror the raw fp32 obs into
-// buf_obs[t] (rollout storage) so no separate copy kernel is needed.
+// Welford-normalised observation, clamped to +-10 (reference
+// running_statistics.py:205-...).
+DEV_INLINE float normalise_obs(float v, float mean, float var) {
+  float sd = sqrtf(fmaxf(var, 1e-6f));
+  return fmaxf(-10.0f, fminf(10.0f, (v - mean) / sd));
+}
+
+// Stage the workgroup's 16 obs rows into LDS as bf16 (zero-padded to K1P),
+// with optional normalisation (mean/var fp32); optionally mirror the raw
+// fp32 obs into buf_obs[t] (rollout storage) so no separate copy kernel is
+// needed.
 DEV_INLINE void stage_obs(const float* __restrict__ obs, int rbase, int OBS,
                           int K1P, bf16_t* __restrict__ Orow, int ostride,
                           const float* __restrict__ nmean,
@@ -192,11 +218,7 @@ DEV_INLINE void stage_obs(const float* __restrict__ obs, int rbase, int OBS,
     if (k < OBS && rbase + r < nrows_total) {
       v = obs[(long)(rbase + r) * OBS + k];
       if (obs_mirror) obs_mirror[(long)(rbase + r) * OBS + k] = v;
-      if (nmean) {
-        float sd = sqrtf(fmaxf(nvar[k], 1e-6f));
-        v = (v - nmean[k]) / sd;
-        v = fmaxf(-10.0f, fminf(10.0f, v));
-      }
+      if (nmean) v = normalise_obs(v, nmean[k], nvar[k]);
     }
     Orow[r * ostride + k] = f2bf(v);
   }
@@ -204,11 +226,13 @@ DEV_INLINE void stage_obs(const float* __restrict__ obs, int rbase, int OBS,
 
 // Critic scalar head via VALU: value[row] = dot(H[row], Wv) + bv.
 // 4 lanes per row (lane l: row l>>2, part l&3), butterfly-reduced.
+// `row_mask` (null, or int[16] in LDS) limits the store to flagged rows.
 template <int HID>
 DEV_INLINE void wave_value_head(const bf16_t* __restrict__ H, int hstride,
-                                const bf16_t* __restrict__ Wv, float bv,
-                                int rbase, float* __restrict__ value_out,
-                                int lane, int B_total) {
+                                const bf16_t* __restrict__ Wv,
+                                const float* __restrict__ bv, int rbase,
+                                float* __restrict__ value_out,
+                                const int* row_mask, int lane, int B_total) {
   int row = lane >> 2;   // 0..15
   int part = lane & 3;   // 0..3
   float acc = 0.0f;
@@ -220,8 +244,149 @@ DEV_INLINE void wave_value_head(const bf16_t* __restrict__ H, int hstride,
   }
   acc += __shfl_xor(acc, 1);
   acc += __shfl_xor(acc, 2);
-  if (part == 0 && value_out && rbase + row < B_total)
-    value_out[rbase + row] = acc + bv;
+  if (part == 0 && value_out && rbase + row < B_total &&
+      (!row_mask || row_mask[row]))
+    value_out[rbase + row] = acc + (bv ? *bv : 0.0f);
+}
+
+// Critic torso from the staged obs tile: O -> H[hbuf] -> H[hbuf + 1], a
+// barrier between the layers. Caller barriers before reading H[hbuf + 1].
+template <int HID>
+DEV_INLINE void critic_torso(MlpLds<HID>& lds, int hbuf,
+                             const bf16_t* __restrict__ W1c,
+                             const float* __restrict__ b1c,
+                             const bf16_t* __restrict__ W2c,
+                             const float* __restrict__ b2c, int K1P, int lane,
+                             int wid) {
+  bf16_t* h0 = &lds.H[hbuf][0][0];
+  bf16_t* h1 = &lds.H[hbuf + 1][0][0];
+  wg_layer<HID, true>(&lds.O[0][0], lds.OS, W1c, b1c, K1P, h0, lds.HS, lane,
+                      wid);
+  __syncthreads();
+  wg_layer<HID, true>(h0, lds.HS, W2c, b2c, HID, h1, lds.HS, lane, wid);
+}
+
+// Actor and critic torsos from the staged obs tile, layer by layer with a
+// barrier after each: actor O -> H[0] -> H[1], critic O -> H[2] -> H[3].
+template <int HID>
+DEV_INLINE void actor_critic_torso(
+    MlpLds<HID>& lds, const bf16_t* __restrict__ W1a,
+    const float* __restrict__ b1a, const bf16_t* __restrict__ W2a,
+    const float* __restrict__ b2a, const bf16_t* __restrict__ W1c,
+    const float* __restrict__ b1c, const bf16_t* __restrict__ W2c,
+    const float* __restrict__ b2c, int K1P, int lane, int wid) {
+  bf16_t* O = &lds.O[0][0];
+  bf16_t* Ha0 = &lds.H[0][0][0];
+  bf16_t* Ha1 = &lds.H[1][0][0];
+  bf16_t* Hc0 = &lds.H[2][0][0];
+  bf16_t* Hc1 = &lds.H[3][0][0];
+  wg_layer<HID, true>(O, lds.OS, W1a, b1a, K1P, Ha0, lds.HS, lane, wid);
+  wg_layer<HID, true>(O, lds.OS, W1c, b1c, K1P, Hc0, lds.HS, lane, wid);
+  __syncthreads();
+  wg_layer<HID, true>(Ha0, lds.HS, W2a, b2a, HID, Ha1, lds.HS, lane, wid);
+  wg_layer<HID, true>(Hc0, lds.HS, W2c, b2c, HID, Hc1, lds.HS, lane, wid);
+  __syncthreads();
+}
+
+// The forward of the step kernels: stage (and mirror) the obs tile, run
+// both torsos, store V(s) from wave 1. Leaves the actor's last hidden layer
+// in lds.H[1] for the head tile. (rollout_step_ant_kernel spells the same
+// sequence out; see there.)
+template <int HID>
+DEV_INLINE void actor_critic_forward(
+    MlpLds<HID>& lds, const float* __restrict__ obs, int rbase, int B,
+    int OBS, const bf16_t* __restrict__ W1a, const float* __restrict__ b1a,
+    const bf16_t* __restrict__ W2a, const float* __restrict__ b2a,
+    const bf16_t* __restrict__ W1c, const float* __restrict__ b1c,
+    const bf16_t* __restrict__ W2c, const float* __restrict__ b2c,
+    const bf16_t* __restrict__ Wvc, const float* __restrict__ bvc,
+    const float* __restrict__ nmean, const float* __restrict__ nvar,
+    float* __restrict__ obs_mirror, float* __restrict__ value_out, int lane,
+    int wid) {
+  const int K1P = k1_padded(OBS);
+  stage_obs(obs, rbase, OBS, K1P, &lds.O[0][0], lds.OS, nmean, nvar,
+            obs_mirror, threadIdx.x, 256, B);
+  __syncthreads();
+  actor_critic_torso<HID>(lds, W1a, b1a, W2a, b2a, W1c, b1c, W2c, b2c, K1P,
+                          lane, wid);
+  if (wid == 1) {
+    wave_value_head<HID>(&lds.H[3][0][0], lds.HS, Wvc, bvc, rbase, value_out,
+                         nullptr, lane, B);
+  }
+}
+
+// The actor head as one 16-column MFMA N-tile (one wave): A fragments from
+// the last hidden layer `Ha1` (LDS), B fragments from Wha [16,HID]. Lane l
+// gets rows (l>>4)*4 + r of column l&15, bias not yet added.
+template <int HID>
+DEV_INLINE f32x4 head_tile(const bf16_t* __restrict__ Ha1,
+                           const bf16_t* __restrict__ Wha, int lane) {
+  constexpr int HS = MlpLds<HID>::HS;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const int arow = lane & 15, ak0 = (lane >> 4) * 8;
+  for (int ks = 0; ks < HID / 32; ++ks) {
+    const bf16x8 a =
+        *reinterpret_cast<const bf16x8*>(Ha1 + arow * HS + ks * 32 + ak0);
+    bf16x8 b = load_w_frag<HID>(Wha, HID, 0, ks, lane);
+    acc = MFMA_BF16_16x16x32(a, b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// Tanh-normal sampling + log-prob on the head tile (one wave). Head
+// packing: Wh = cat([loc.weight, scale.weight]) [16,HID] bf16, bh =
+// cat([loc.bias, scale.bias]) [16] fp32, so the tile is
+// [loc(0:ACT) | pad | scale(8:8+ACT)], ACT <= 8. For its rows g*4 + r
+// (g = lane>>4) lane col = lane&15 gets a_val[r], the action component of
+// dim col (valid for col < ACT), and logp[r], the row's log pi(a|s)
+// summed over dims (valid for col < 8). Philox stream 2, counter
+// rowblk*16 + col, `draw`: one block serves the 4 rows of a (row-block,
+// dim).
+DEV_INLINE void tanh_normal_sample(f32x4 acc, const float* __restrict__ bha,
+                                   int rbase, int lane, int ACT,
+                                   float min_scale, float aff_scale,
+                                   float aff_shift, float log_aff_scale,
+                                   int greedy, uint64_t seed, uint32_t draw,
+                                   float* a_val, float* logp_out) {
+  const int col = lane & 15;  // col<8: loc dim, col>=8: scale dim col-8
+  const int g = lane >> 4;
+  float bh = bha[col];
+  float out[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) out[r] = acc[r] + bh;
+  // pair loc (lane c) with scale (lane c+8): shfl within the 16-lane group
+  const int src_lane = (lane & 48) | (((lane & 15) + 8) & 15);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float loc = out[r];
+    float spre = __shfl(out[r], src_lane, 64);
+    float logp = 0.0f;
+    a_val[r] = 0.0f;
+    if (col < 8) {
+      float sigma = softplus_fast(spre) + min_scale;
+      // 4 normals for this (row-block, dim) from one philox block
+      int rowblk = (rbase + g * 4) >> 2;  // global row / 4
+      Rng4 u = philox_uniform4(seed, 2u, (uint32_t)(rowblk * 16 + col), draw);
+      float n[4];
+      box_muller(u.a, u.b, &n[0], &n[1]);
+      box_muller(u.c, u.d, &n[2], &n[3]);
+      float eps = greedy ? 0.0f : n[r];
+      float uu = loc + sigma * eps;
+      a_val[r] = tanh_fast(uu) * aff_scale + aff_shift;
+      // log N(u;loc,sigma) - log|d a/d u|
+      float log_det =
+          2.0f * (0.6931471805599453f - uu - softplus_fast(-2.0f * uu)) +
+          log_aff_scale;
+      logp = -0.5f * eps * eps - __logf(sigma) - 0.9189385332046727f -
+             log_det;
+    }
+    if (col >= ACT && col < 8) logp = 0.0f;  // unused dims (ACT<8)
+    // reduce logp over dims (lanes col 0..7 of this group)
+    logp += __shfl_xor(logp, 1);
+    logp += __shfl_xor(logp, 2);
+    logp += __shfl_xor(logp, 4);
+    logp_out[r] = logp;
+  }
 }
 
 // The fused policy step. Writes, for rollout step t:
@@ -229,8 +394,6 @@ DEV_INLINE void wave_value_head(const bf16_t* __restrict__ H, int hstride,
 //   action_out    = tanh-normal sample     ([B,ACT] fp32, env input + buffer)
 //   logp_out      = log pi(a|s)            ([B] fp32)
 //   value_out     = V(s)                   ([B] fp32)
-// Head packing: Wh = cat([loc.weight, scale.weight]) [16,HID] bf16,
-// bh = cat([loc.bias, scale.bias]) [16] fp32. ACT <= 8.
 template <int HID>
 __launch_bounds__(256, 2) __global__ void policy_value_step_kernel(
     const float* __restrict__ obs,        // [B, OBS]
@@ -258,86 +421,25 @@ __launch_bounds__(256, 2) __global__ void policy_value_step_kernel(
   // rollout bumps the base ONCE per replay (bump_add) instead of paying a
   // 1-thread bump kernel per step (~5 us each, ~2 ms/update-step)
   const uint32_t draw = (draw_buf ? *draw_buf : 0u) + draw_offset;
-  const int K1P = (OBS + 31) & ~31;
 
-  bf16_t* O = &lds.O[0][0];
-  constexpr int OS = K1P_MAX + OPAD;
-  constexpr int HS = HID + HPAD;
-  bf16_t* Ha0 = &lds.H[0][0][0];
-  bf16_t* Ha1 = &lds.H[1][0][0];
-  bf16_t* Hc0 = &lds.H[2][0][0];
-  bf16_t* Hc1 = &lds.H[3][0][0];
+  actor_critic_forward<HID>(lds, obs, rbase, B, OBS, W1a, b1a, W2a, b2a, W1c,
+                            b1c, W2c, b2c, Wvc, bvc, nmean, nvar, obs_mirror,
+                            value_out, lane, wid);
 
-  stage_obs(obs, rbase, OBS, K1P, O, OS, nmean, nvar, obs_mirror,
-            threadIdx.x, 256, B);
-  __syncthreads();
-
-  // ---- torsos (split-N across waves; ping/pong LDS buffers)
-  wg_layer<HID, true>(O, OS, W1a, b1a, K1P, Ha0, HS, lane, wid);
-  wg_layer<HID, true>(O, OS, W1c, b1c, K1P, Hc0, HS, lane, wid);
-  __syncthreads();
-  wg_layer<HID, true>(Ha0, HS, W2a, b2a, HID, Ha1, HS, lane, wid);
-  wg_layer<HID, true>(Hc0, HS, W2c, b2c, HID, Hc1, HS, lane, wid);
-  __syncthreads();
-
-  // ---- critic scalar head on wave 1 (VALU dot)
-  if (wid == 1) {
-    wave_value_head<HID>(Hc1, HS, Wvc, bvc ? *bvc : 0.0f, rbase, value_out,
-                         lane, B);
-  }
-
-  // ---- actor head + tanh-normal sample on wave 0:
-  // one 16-col N-tile = [loc(0:ACT) | pad | scale(8:8+ACT)]
+  // ---- actor head + tanh-normal sample on wave 0
   if (wid == 0) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int arow = lane & 15, ak0 = (lane >> 4) * 8;
-    for (int ks = 0; ks < HID / 32; ++ks) {
-      const bf16x8 a =
-          *reinterpret_cast<const bf16x8*>(Ha1 + arow * HS + ks * 32 + ak0);
-      bf16x8 b = load_w_frag<HID>(Wha, HID, 0, ks, lane);
-      acc = MFMA_BF16_16x16x32(a, b, acc, 0, 0, 0);
-    }
-    const int col = lane & 15;  // col<8: loc dim, col>=8: scale dim col-8
+    float a_val[4], logp[4];
+    tanh_normal_sample(head_tile<HID>(&lds.H[1][0][0], Wha, lane), bha, rbase,
+                       lane, ACT, min_scale, aff_scale, aff_shift,
+                       log_aff_scale, greedy, seed, draw, a_val, logp);
+    const int col = lane & 15;
     const int g = lane >> 4;
-    float bh = bha[col];
-    float out[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[r] = acc[r] + bh;
-    // pair loc (lane c) with scale (lane c+8): shfl within the 16-lane group
-    const int src_lane = (lane & 48) | (((lane & 15) + 8) & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float loc = out[r];
-      float spre = __shfl(out[r], src_lane, 64);
-      float logp = 0.0f;
-      float a_val = 0.0f;
-      if (col < 8) {
-        float sigma = softplus_fast(spre) + min_scale;
-        // 4 normals for this (row-block, dim) from one philox block
-        int rowblk = (rbase + g * 4) >> 2;  // global row / 4
-        Rng4 u = philox_uniform4(seed, 2u, (uint32_t)(rowblk * 16 + col), draw);
-        float n[4];
-        box_muller(u.a, u.b, &n[0], &n[1]);
-        box_muller(u.c, u.d, &n[2], &n[3]);
-        float eps = greedy ? 0.0f : n[r];
-        float uu = loc + sigma * eps;
-        a_val = tanh_fast(uu) * aff_scale + aff_shift;
-        // log N(u;loc,sigma) - log|d a/d u|
-        float log_det =
-            2.0f * (0.6931471805599453f - uu - softplus_fast(-2.0f * uu)) +
-            log_aff_scale;
-        logp = -0.5f * eps * eps - __logf(sigma) -
-               0.9189385332046727f - log_det;
-      }
-      if (col >= ACT && col < 8) logp = 0.0f;  // unused dims (ACT<8)
-      // reduce logp over dims (lanes col 0..7 of this group)
-      logp += __shfl_xor(logp, 1);
-      logp += __shfl_xor(logp, 2);
-      logp += __shfl_xor(logp, 4);
       int grow = rbase + g * 4 + r;
       if (grow < B) {
-        if (col < ACT) action_out[(long)grow * ACT + col] = a_val;
-        if (col == 0) logp_out[grow] = logp;
+        if (col < ACT) action_out[(long)grow * ACT + col] = a_val[r];
+        if (col == 0) logp_out[grow] = logp[r];
       }
     }
   }
@@ -358,39 +460,29 @@ __launch_bounds__(256, 2) __global__ void value_forward_kernel(
   const int wid = threadIdx.x >> 6;
   const int rbase = blockIdx.x * 16;
   if (rbase >= B) return;
-  const int K1P = (OBS + 31) & ~31;
-  bf16_t* O = &lds.O[0][0];
-  bf16_t* H0 = &lds.H[0][0][0];
-  bf16_t* H1 = &lds.H[1][0][0];
-  constexpr int OS = K1P_MAX + OPAD;
-  constexpr int HS = HID + HPAD;
-  stage_obs(obs, rbase, OBS, K1P, O, OS, nmean, nvar, nullptr, threadIdx.x,
-            256, B);
+  const int K1P = k1_padded(OBS);
+  stage_obs(obs, rbase, OBS, K1P, &lds.O[0][0], lds.OS, nmean, nvar, nullptr,
+            threadIdx.x, 256, B);
   __syncthreads();
-  wg_layer<HID, true>(O, OS, W1c, b1c, K1P, H0, HS, lane, wid);
-  __syncthreads();
-  wg_layer<HID, true>(H0, HS, W2c, b2c, HID, H1, HS, lane, wid);
+  critic_torso<HID>(lds, 0, W1c, b1c, W2c, b2c, K1P, lane, wid);
   __syncthreads();
   if (wid == 0) {
-    wave_value_head<HID>(H1, HS, Wvc, bvc ? *bvc : 0.0f, rbase, value_out,
-                         lane, B);
+    wave_value_head<HID>(&lds.H[1][0][0], lds.HS, Wvc, bvc, rbase, value_out,
+                         nullptr, lane, B);
   }
 }
 
 // --------------------------------------- fused rollout step (Ant)
 //
 // ONE launch per rollout step: actor fwd + tanh-normal sample + critic fwd
-// (MFMA, all 4 waves) -> Ant physics + autoreset + episode metrics (16 env
-// threads of the workgroup; everything is per-env-row independent, so no
-// grid-wide sync is needed) -> critic fwd on the pre-reset next_obs
-// (bootstrap). Replaces the 3-kernel (policy/env/value) chain: fewer
-// launches, 4x more CUs on the physics (256 WGs vs 64), and next_obs never
-// round-trips through HBM (it stays in LDS for the bootstrap pass).
-// RPW = batch rows (envs) per workgroup (16 = full MFMA M-tile; the 8-row
-// variant exists for the occupancy experiment documented in the launcher
-// -- it lost, because a half-empty tile still issues the full instruction
-// stream).
-template <int HID, int RPW>
+// (MFMA, all 4 waves) -> Ant physics + autoreset + episode metrics (wave 0,
+// 4 lanes per env; everything is per-env-row independent, so no grid-wide
+// sync is needed) -> critic fwd on the pre-reset next_obs (bootstrap).
+// Replaces the 3-kernel (policy/env/value) chain: fewer launches, 4x more
+// CUs on the physics (256 WGs vs 64), and next_obs never round-trips
+// through HBM (it stays in LDS for the bootstrap pass). OBS and ACT are
+// the Ant's (ANT_OBS, ANT_ACT).
+template <int HID>
 __launch_bounds__(256, 2) __global__ void rollout_step_ant_kernel(
     float* __restrict__ obs_io,          // [B, 27] env obs buffer (in/out)
     float* __restrict__ env_state,       // [B, 29]
@@ -418,90 +510,53 @@ __launch_bounds__(256, 2) __global__ void rollout_step_ant_kernel(
   __shared__ MlpLds<HID> lds;
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
-  const int rbase = blockIdx.x * RPW;
+  const int rbase = blockIdx.x * 16;
   if (rbase >= B) return;
-  // rows [RPW, 16) of the tile belong to the NEXT workgroup at RPW=8:
-  // cap every per-row bound so they are staged as zeros and never written
-  const int Bcap = min(B, rbase + RPW);
   const uint32_t pdraw = *policy_draw + draw_offset;
   const uint32_t edraw = *env_draw + draw_offset;
-  const int K1P = (OBS + 31) & ~31;
 
+  if (threadIdx.x == 0) lds.any_done = 0;
+
+  // ---- policy + value: the forward and epilogue of policy_value_step_kernel.
+  // The body of actor_critic_forward is spelled out here: routed through the
+  // helper, this kernel gets another register allocation (138 -> 106 VGPRs,
+  // 3 -> 4 waves/SIMD at HID 256), which this refactor must not change.
+  // tests/test_fused_gpu.py pins the two bit-equal at every width.
+  const int K1P = k1_padded(OBS);
   bf16_t* O = &lds.O[0][0];
-  constexpr int OS = K1P_MAX + OPAD;
-  constexpr int HS = HID + HPAD;
   bf16_t* Ha0 = &lds.H[0][0][0];
   bf16_t* Ha1 = &lds.H[1][0][0];
   bf16_t* Hc0 = &lds.H[2][0][0];
   bf16_t* Hc1 = &lds.H[3][0][0];
-
-  if (threadIdx.x == 0) lds.any_done = 0;
-  stage_obs(obs_io, rbase, OBS, K1P, O, OS, nullptr, nullptr, buf_obs,
-            threadIdx.x, 256, Bcap);
+  stage_obs(obs_io, rbase, OBS, K1P, O, lds.OS, nullptr, nullptr, buf_obs,
+            threadIdx.x, 256, B);
   __syncthreads();
-
-  // ---- policy + value (same structure as policy_value_step_kernel)
-  wg_layer<HID, true>(O, OS, W1a, b1a, K1P, Ha0, HS, lane, wid);
-  wg_layer<HID, true>(O, OS, W1c, b1c, K1P, Hc0, HS, lane, wid);
+  wg_layer<HID, true>(O, lds.OS, W1a, b1a, K1P, Ha0, lds.HS, lane, wid);
+  wg_layer<HID, true>(O, lds.OS, W1c, b1c, K1P, Hc0, lds.HS, lane, wid);
   __syncthreads();
-  wg_layer<HID, true>(Ha0, HS, W2a, b2a, HID, Ha1, HS, lane, wid);
-  wg_layer<HID, true>(Hc0, HS, W2c, b2c, HID, Hc1, HS, lane, wid);
+  wg_layer<HID, true>(Ha0, lds.HS, W2a, b2a, HID, Ha1, lds.HS, lane, wid);
+  wg_layer<HID, true>(Hc0, lds.HS, W2c, b2c, HID, Hc1, lds.HS, lane, wid);
   __syncthreads();
-
   if (wid == 1) {
-    wave_value_head<HID>(Hc1, HS, Wvc, bvc ? *bvc : 0.0f, rbase, buf_value,
-                         lane, Bcap);
+    wave_value_head<HID>(Hc1, lds.HS, Wvc, bvc, rbase, buf_value, nullptr,
+                         lane, B);
   }
   if (wid == 0) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int arow = lane & 15, ak0 = (lane >> 4) * 8;
-    for (int ks = 0; ks < HID / 32; ++ks) {
-      const bf16x8 aa =
-          *reinterpret_cast<const bf16x8*>(Ha1 + arow * HS + ks * 32 + ak0);
-      bf16x8 bb = load_w_frag<HID>(Wha, HID, 0, ks, lane);
-      acc = MFMA_BF16_16x16x32(aa, bb, acc, 0, 0, 0);
-    }
+    float a_val[4], logp[4];
+    tanh_normal_sample(head_tile<HID>(Ha1, Wha, lane), bha, rbase, lane, ACT,
+                       min_scale, aff_scale, aff_shift, log_aff_scale, 0,
+                       policy_seed, pdraw, a_val, logp);
     const int col = lane & 15;
     const int g = lane >> 4;
-    float bh = bha[col];
-    float out[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[r] = acc[r] + bh;
-    const int src_lane = (lane & 48) | (((lane & 15) + 8) & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float loc = out[r];
-      float spre = __shfl(out[r], src_lane, 64);
-      float logp = 0.0f;
-      float a_val = 0.0f;
-      if (col < 8) {
-        float sigma = softplus_fast(spre) + min_scale;
-        int rowblk = (rbase + g * 4) >> 2;
-        Rng4 u = philox_uniform4(policy_seed, 2u, (uint32_t)(rowblk * 16 + col),
-                                 pdraw);
-        float n[4];
-        box_muller(u.a, u.b, &n[0], &n[1]);
-        box_muller(u.c, u.d, &n[2], &n[3]);
-        float eps = n[r];
-        float uu = loc + sigma * eps;
-        a_val = tanh_fast(uu) * aff_scale + aff_shift;
-        float log_det =
-            2.0f * (0.6931471805599453f - uu - softplus_fast(-2.0f * uu)) +
-            log_aff_scale;
-        logp = -0.5f * eps * eps - __logf(sigma) - 0.9189385332046727f -
-               log_det;
-      }
-      if (col >= ACT && col < 8) logp = 0.0f;
-      logp += __shfl_xor(logp, 1);
-      logp += __shfl_xor(logp, 2);
-      logp += __shfl_xor(logp, 4);
       int grow = rbase + g * 4 + r;
-      if (grow < Bcap) {
+      if (grow < B) {
         if (col < ACT) {
-          buf_action[(long)grow * ACT + col] = a_val;
-          lds.act[g * 4 + r][col] = a_val;
+          buf_action[(long)grow * ACT + col] = a_val[r];
+          lds.act[g * 4 + r][col] = a_val[r];
         }
-        if (col == 0) buf_logp[grow] = logp;
+        if (col == 0) buf_logp[grow] = logp[r];
       }
     }
   }
@@ -513,7 +568,7 @@ __launch_bounds__(256, 2) __global__ void rollout_step_ant_kernel(
     int row = threadIdx.x >> 2;
     int leg = threadIdx.x & 3;
     int b = rbase + row;
-    if (b < Bcap) {
+    if (b < B) {
       float es[ANT_STATE];
 #pragma unroll
       for (int i = 0; i < ANT_STATE; ++i) es[i] = env_state[b * ANT_STATE + i];
@@ -564,29 +619,33 @@ __launch_bounds__(256, 2) __global__ void rollout_step_ant_kernel(
   }
   __syncthreads();
 
-  // ---- bootstrap critic, only when this WG saw an episode end
+  // ---- bootstrap critic, only when this WG saw an episode end; stores
+  // only the done rows (others get the shifted next-step value from the
+  // engine)
   if (lds.any_done) {
-    wg_layer<HID, true>(O, OS, W1c, b1c, K1P, Hc0, HS, lane, wid);
-    __syncthreads();
-    wg_layer<HID, true>(Hc0, HS, W2c, b2c, HID, Hc1, HS, lane, wid);
+    critic_torso<HID>(lds, 2, W1c, b1c, W2c, b2c, K1P, lane, wid);
     __syncthreads();
     if (wid == 0) {
-      // value head, but store only the done rows (others get the shifted
-      // next-step value from the engine)
-      int row = lane >> 2;
-      int part = lane & 3;
-      float acc = 0.0f;
-      for (int c = part * (HID / 4); c < (part + 1) * (HID / 4); c += 8) {
-        bf16x8 h = *reinterpret_cast<const bf16x8*>(Hc1 + row * HS + c);
-        bf16x8 w = *reinterpret_cast<const bf16x8*>(Wvc + c);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += bf2f(h[j]) * bf2f(w[j]);
-      }
-      acc += __shfl_xor(acc, 1);
-      acc += __shfl_xor(acc, 2);
-      if (part == 0 && rbase + row < Bcap && lds.done[row])
-        buf_bootstrap[rbase + row] = acc + (bvc ? *bvc : 0.0f);
+      wave_value_head<HID>(&lds.H[3][0][0], lds.HS, Wvc, bvc, rbase,
+                           buf_bootstrap, lds.done, lane, B);
     }
+  }
+}
+
+// Runtime HID -> template instantiation, for every HID-templated kernel:
+// `launch` is a generic lambda called with std::integral_constant<int, HID>.
+// There is deliberately no default width: a HID outside the set throws. The
+// user-facing check is check_fused_mlp in bind.cpp, which raises first.
+template <class Launch>
+static void dispatch_hid(int HID, Launch&& launch) {
+  switch (HID) {
+    case 128: launch(std::integral_constant<int, 128>{}); break;
+    case 256: launch(std::integral_constant<int, 256>{}); break;
+    case 512: launch(std::integral_constant<int, 512>{}); break;
+    default:
+      throw std::invalid_argument(
+          "fused MLP kernels are instantiated for HID 128/256/512, got " +
+          std::to_string(HID));
   }
 }
 
@@ -604,61 +663,23 @@ extern "C" void launch_rollout_step_ant(
     unsigned int* policy_draw, unsigned int* env_draw,
     unsigned int draw_offset, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  // RPW=8 was tried to double the grid for stall overlap at B=4096
-  // (1 WG/CU): measured WORSE (rollout 4.0 -> 5.4 ms) because each WG
-  // still issues the full 16-row tile instruction stream -- halving the
-  // rows doubles total issue. 16 stays.
-  int rpw = 16;
-  dim3 grid((B + rpw - 1) / rpw), block(256);
-  if (HID == 256 && rpw == 8) {
-    hipLaunchKernelGGL((rollout_step_ant_kernel<256, 8>), grid, block, 0, s,
-                       obs_io, env_state, step_count, ep_return, ep_length,
-                       last_ep_return, last_ep_length, (const bf16_t*)W1a,
-                       b1a, (const bf16_t*)W2a, b2a, (const bf16_t*)Wha, bha,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, buf_obs, buf_action, buf_logp,
-                       buf_value, buf_bootstrap, buf_reward, buf_discount,
-                       buf_steptype, B, OBS, ACT, max_episode_steps,
-                       min_scale, aff_scale, aff_shift, log_aff_scale,
-                       policy_seed, env_seed, policy_draw, env_draw,
-                       draw_offset);
-  } else if (HID == 256) {
-    hipLaunchKernelGGL((rollout_step_ant_kernel<256, 16>), grid, block, 0, s,
-                       obs_io, env_state, step_count, ep_return, ep_length,
-                       last_ep_return, last_ep_length, (const bf16_t*)W1a,
-                       b1a, (const bf16_t*)W2a, b2a, (const bf16_t*)Wha, bha,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, buf_obs, buf_action, buf_logp,
-                       buf_value, buf_bootstrap, buf_reward, buf_discount,
-                       buf_steptype, B, OBS, ACT, max_episode_steps,
-                       min_scale, aff_scale, aff_shift, log_aff_scale,
-                       policy_seed, env_seed, policy_draw, env_draw,
-                       draw_offset);
-  } else if (rpw == 8) {
-    hipLaunchKernelGGL((rollout_step_ant_kernel<128, 8>), grid, block, 0, s,
-                       obs_io, env_state, step_count, ep_return, ep_length,
-                       last_ep_return, last_ep_length, (const bf16_t*)W1a,
-                       b1a, (const bf16_t*)W2a, b2a, (const bf16_t*)Wha, bha,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, buf_obs, buf_action, buf_logp,
-                       buf_value, buf_bootstrap, buf_reward, buf_discount,
-                       buf_steptype, B, OBS, ACT, max_episode_steps,
-                       min_scale, aff_scale, aff_shift, log_aff_scale,
-                       policy_seed, env_seed, policy_draw, env_draw,
-                       draw_offset);
-  } else {
-    hipLaunchKernelGGL((rollout_step_ant_kernel<128, 16>), grid, block, 0, s,
-                       obs_io, env_state, step_count, ep_return, ep_length,
-                       last_ep_return, last_ep_length, (const bf16_t*)W1a,
-                       b1a, (const bf16_t*)W2a, b2a, (const bf16_t*)Wha, bha,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, buf_obs, buf_action, buf_logp,
-                       buf_value, buf_bootstrap, buf_reward, buf_discount,
-                       buf_steptype, B, OBS, ACT, max_episode_steps,
-                       min_scale, aff_scale, aff_shift, log_aff_scale,
-                       policy_seed, env_seed, policy_draw, env_draw,
-                       draw_offset);
-  }
+  // 16 envs per workgroup (one full M-tile). 8 per workgroup, to double the
+  // grid, measured worse: rollout 4.0 -> 5.4 ms, a half-empty tile still
+  // issues the full instruction stream.
+  dim3 grid((B + 15) / 16), block(256);
+  dispatch_hid(HID, [&](auto hid) {
+    hipLaunchKernelGGL(rollout_step_ant_kernel<decltype(hid)::value>, grid,
+                       block, 0, s, obs_io, env_state, step_count, ep_return,
+                       ep_length, last_ep_return, last_ep_length,
+                       (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
+                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
+                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
+                       buf_obs, buf_action, buf_logp, buf_value,
+                       buf_bootstrap, buf_reward, buf_discount, buf_steptype,
+                       B, OBS, ACT, max_episode_steps, min_scale, aff_scale,
+                       aff_shift, log_aff_scale, policy_seed, env_seed,
+                       policy_draw, env_draw, draw_offset);
+  });
 }
 
 // ------------------------------------ fused Linear+SiLU forward (update)
@@ -812,7 +833,41 @@ extern "C" __global__ void silu_bwd_kernel(const bf16_t* __restrict__ dh,
 
 // Fused minibatch gather: one kernel replaces 6 index_selects. Gathers the
 // permuted rows of the flat rollout storage for one minibatch (obs -> bf16
-// GEMM input; the scalar fields fp32).
+// GEMM input, normalised if asked; the scalar fields fp32). One wave per
+// row; obs_out is [mb, OBS_PAD] (K padded to the MFMA K-step, pad columns
+// zero-filled to match the padded W1 layout). `copy_action(src, row, lane)`
+// is the only part that depends on the action space.
+template <class CopyAction>
+DEV_INLINE void ppo_gather_body(
+    const long* __restrict__ idx, int mb_size,
+    const float* __restrict__ obs, int OBS, int OBS_PAD,
+    const float* __restrict__ logp, const float* __restrict__ value,
+    const float* __restrict__ adv, const float* __restrict__ targets,
+    bf16_t* __restrict__ obs_out, float* __restrict__ logp_out,
+    float* __restrict__ value_out, float* __restrict__ adv_out,
+    float* __restrict__ targets_out, const float* __restrict__ nmean,
+    const float* __restrict__ nvar, CopyAction copy_action) {
+  int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  int lane = threadIdx.x & 63;
+  if (row >= mb_size) return;
+  long src = idx[row];
+  for (int k = lane; k < OBS_PAD; k += 64) {
+    float v = 0.0f;
+    if (k < OBS) {
+      v = obs[src * OBS + k];
+      if (nmean) v = normalise_obs(v, nmean[k], nvar[k]);
+    }
+    obs_out[(long)row * OBS_PAD + k] = f2bf(v);
+  }
+  copy_action(src, row, lane);
+  if (lane == 0) {
+    logp_out[row] = logp[src];
+    value_out[row] = value[src];
+    adv_out[row] = adv[src];
+    targets_out[row] = targets[src];
+  }
+}
+
 extern "C" __global__ void ppo_gather_kernel(
     const long* __restrict__ idx, int mb_size,
     const float* __restrict__ obs, int OBS, int OBS_PAD,
@@ -823,45 +878,92 @@ extern "C" __global__ void ppo_gather_kernel(
     float* __restrict__ logp_out, float* __restrict__ value_out,
     float* __restrict__ adv_out, float* __restrict__ targets_out,
     const float* __restrict__ nmean, const float* __restrict__ nvar) {
-  // one wave per row; obs_out is [mb, OBS_PAD] (K padded to the MFMA
-  // K-step, pad columns zero-filled to match the padded W1 layout)
-  int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int lane = threadIdx.x & 63;
-  if (row >= mb_size) return;
-  long src = idx[row];
-  for (int k = lane; k < OBS_PAD; k += 64) {
-    float v = 0.0f;
-    if (k < OBS) {
-      v = obs[src * OBS + k];
-      if (nmean) {
-        float sd = sqrtf(fmaxf(nvar[k], 1e-6f));
-        v = fmaxf(-10.0f, fminf(10.0f, (v - nmean[k]) / sd));
-      }
-    }
-    obs_out[(long)row * OBS_PAD + k] = f2bf(v);
-  }
-  if (lane < ACT) action_out[(long)row * ACT + lane] = action[src * ACT + lane];
-  if (lane == 0) {
-    logp_out[row] = logp[src];
-    value_out[row] = value[src];
-    adv_out[row] = adv[src];
-    targets_out[row] = targets[src];
-  }
+  ppo_gather_body(idx, mb_size, obs, OBS, OBS_PAD, logp, value, adv, targets,
+                  obs_out, logp_out, value_out, adv_out, targets_out, nmean,
+                  nvar, [=](long src, int row, int lane) {
+                    if (lane < ACT)
+                      action_out[(long)row * ACT + lane] =
+                          action[src * ACT + lane];
+                  });
 }
 
 // ---------------------------------------------- fused PPO head + losses
 //
 // One THREAD per sample row. The head projections themselves are GEMMs and
 // run on hipBLASLt in the engine (heads = H2a @ Wha^T + bha -> [B,16],
-// v = H2c @ Wvc + bvc -> [B]); this kernel does the remaining per-row
-// scalar math: tanh-normal log-prob of the stored action, PPO clip loss
-// (losses.py ppo_clip_loss), clipped value loss, MC entropy, and the
-// analytic gradients d(total)/d{loc, scale_pre, v} (verified against
-// autograd in tests/test_fused_math.py). dH2a/dH2c are then GEMMs again
-// (dhead @ Wha, dv @ Wvc) in the engine.
+// v = H2c @ Wvc + bvc -> [B]); the head-loss kernels do the remaining
+// per-row scalar math: log-prob of the stored action, PPO clip loss
+// (losses.py ppo_clip_loss), clipped value loss, entropy, and the analytic
+// gradients d(total)/d{head outputs, v} (verified against autograd in
+// tests/test_fused_math.py). dH2a/dH2c are then GEMMs again (dhead @ Wha,
+// dv @ Wvc) in the engine.
 //
 // Gradient scale: total = a_loss - ent_coef*entropy + vf_coef*v_loss,
-// all means over the minibatch (inv_B folded in here).
+// all means over the minibatch (inv_B folded in here). The clip loss, the
+// value loss and the metrics reduction are the same for both heads.
+
+// PPO clip loss of one row; *dl_dlogp = d(loss)/d(logp_new) * inv_B.
+DEV_INLINE float ppo_clip_loss_row(float logp_new, float old_logp, float A,
+                                   float clip_eps, float inv_B,
+                                   float* dl_dlogp) {
+  float ratio = __expf(logp_new - old_logp);
+  float r_clip = fmaxf(1.0f - clip_eps, fminf(1.0f + clip_eps, ratio));
+  float l1 = ratio * A, l2 = r_clip * A;
+  float d;  // autograd semantics: min picks l1 branch on tie
+  if (l1 <= l2) {
+    d = -ratio * A;
+  } else {
+    d = (ratio > 1.0f - clip_eps && ratio < 1.0f + clip_eps) ? -ratio * A
+                                                             : 0.0f;
+  }
+  *dl_dlogp = d * inv_B;
+  return -fminf(l1, l2);
+}
+
+// Clipped value loss of one row; *dv = d(loss)/d(v_pred) * dv_scale.
+DEV_INLINE float clipped_value_loss_row(float v_pred, float ov, float tg,
+                                        float clip_eps, float dv_scale,
+                                        float* dv) {
+  float v_clip = ov + fmaxf(-clip_eps, fminf(clip_eps, v_pred - ov));
+  float e1 = (v_pred - tg), e2 = (v_clip - tg);
+  float sq1 = e1 * e1, sq2 = e2 * e2;
+  float d;
+  if (sq1 >= sq2) {
+    d = e1;
+  } else {
+    d = (fabsf(v_pred - ov) < clip_eps) ? e2 : 0.0f;
+  }
+  *dv = d * dv_scale;
+  return 0.5f * fmaxf(sq1, sq2);
+}
+
+// Loss metrics [actor_loss, value_loss, entropy]: wave-level pre-reduce,
+// one atomic per wave; inactive lanes join the shuffles with zeros.
+// Optional: 512 waves funnelling atomics into the same 3 words serialise
+// across all XCDs, so the engine requests metrics only on the minibatch it
+// actually reports (the last one).
+DEV_INLINE void add_loss_metrics(float* __restrict__ metrics, bool active,
+                                 float a_loss, float v_loss, float ent,
+                                 float inv_B) {
+  if (!metrics) return;
+  float m0 = active ? a_loss * inv_B : 0.0f;
+  float m1 = active ? v_loss * inv_B : 0.0f;
+  float m2 = active ? ent * inv_B : 0.0f;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    m0 += __shfl_down(m0, off);
+    m1 += __shfl_down(m1, off);
+    m2 += __shfl_down(m2, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&metrics[0], m0);
+    atomicAdd(&metrics[1], m1);
+    atomicAdd(&metrics[2], m2);
+  }
+}
+
+// Tanh-normal head: log-prob of the stored action, MC entropy, gradients
+// d(total)/d{loc, scale_pre, v}.
 extern "C" __global__ void ppo_head_loss_kernel(
     const bf16_t* __restrict__ heads,    // [B, 16] = loc(0:8)|spre(8:16)
     const bf16_t* __restrict__ v_in,     // [B] critic head output
@@ -879,8 +981,7 @@ extern "C" __global__ void ppo_head_loss_kernel(
     float inv_B, uint64_t seed, const unsigned int* __restrict__ draw_buf,
     unsigned int draw_offset) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = row < B;  // inactive lanes still join the metric
-                                // shuffle-reduce (contribute zeros)
+  const bool active = row < B;
   const uint32_t draw = (draw_buf ? *draw_buf : 0u) + draw_offset;
 
   // ---- per-dim tanh-normal forward
@@ -947,37 +1048,13 @@ extern "C" __global__ void ppo_head_loss_kernel(
            log_det_e;
   }
 
-  // ---- PPO clip loss
-  float A = active ? adv[row] : 0.0f;
-  float ratio = __expf(logp_new - (active ? old_logp[row] : 0.0f));
-  float r_clip = fmaxf(1.0f - clip_eps, fminf(1.0f + clip_eps, ratio));
-  float l1 = ratio * A, l2 = r_clip * A;
-  float a_loss = -fminf(l1, l2);
-  float dl_dlogp;  // autograd semantics: min picks l1 branch on tie
-  if (l1 <= l2) {
-    dl_dlogp = -ratio * A;
-  } else {
-    dl_dlogp = (ratio > 1.0f - clip_eps && ratio < 1.0f + clip_eps)
-                   ? -ratio * A
-                   : 0.0f;
-  }
-  dl_dlogp *= inv_B;
-
-  // ---- clipped value loss
-  float v_pred = active ? bf2f(v_in[row]) : 0.0f;
-  float ov = active ? old_value[row] : 0.0f;
-  float tg = active ? targets[row] : 0.0f;
-  float v_clip = ov + fmaxf(-clip_eps, fminf(clip_eps, v_pred - ov));
-  float e1 = (v_pred - tg), e2 = (v_clip - tg);
-  float sq1 = e1 * e1, sq2 = e2 * e2;
-  float v_loss = 0.5f * fmaxf(sq1, sq2);
-  float dv;
-  if (sq1 >= sq2) {
-    dv = e1;
-  } else {
-    dv = (fabsf(v_pred - ov) < clip_eps) ? e2 : 0.0f;
-  }
-  dv *= vf_coef * inv_B;
+  float dl_dlogp, dv;
+  float a_loss = ppo_clip_loss_row(logp_new, active ? old_logp[row] : 0.0f,
+                                   active ? adv[row] : 0.0f, clip_eps, inv_B,
+                                   &dl_dlogp);
+  float v_loss = clipped_value_loss_row(
+      active ? bf2f(v_in[row]) : 0.0f, active ? old_value[row] : 0.0f,
+      active ? targets[row] : 0.0f, clip_eps, vf_coef * inv_B, &dv);
 
   // ---- analytic head gradients
   bf16x8 dl8, ds8;
@@ -1005,26 +1082,7 @@ extern "C" __global__ void ppo_head_loss_kernel(
     if (dv16_out) dv16_out[(long)row * 16] = f2bf(dv);
   }
 
-  // ---- loss metrics (wave-level pre-reduce, one atomic per wave).
-  // Optional: 512 waves funnelling atomics into the same 3 words
-  // serialise across all XCDs, so the engine requests metrics only on
-  // the minibatch it actually reports (the last one).
-  if (metrics) {
-    float m0 = active ? a_loss * inv_B : 0.0f;
-    float m1 = active ? v_loss * inv_B : 0.0f;
-    float m2 = active ? ent * inv_B : 0.0f;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      m0 += __shfl_down(m0, off);
-      m1 += __shfl_down(m1, off);
-      m2 += __shfl_down(m2, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&metrics[0], m0);
-      atomicAdd(&metrics[1], m1);
-      atomicAdd(&metrics[2], m2);
-    }
-  }
+  add_loss_metrics(metrics, active, a_loss, v_loss, ent, inv_B);
 }
 
 // --------------------------------------------------------- host launchers
@@ -1036,6 +1094,21 @@ extern "C" __global__ void bump_u32_kernel2(unsigned int* p) {
 extern "C" __global__ void bump_add_kernel(unsigned int* p, unsigned int n) {
   if (blockIdx.x == 0 && threadIdx.x == 0) (*p) += n;
 }
+
+// Advance a draw counter by one after the kernel that consumed it.
+static void bump_draw(unsigned int* draw_buf, int do_bump, hipStream_t s) {
+  if (draw_buf && do_bump)
+    hipLaunchKernelGGL(bump_u32_kernel2, dim3(1), dim3(1), 0, s, draw_buf);
+}
+
+// Grid of the 8-wide grid-stride SiLU kernels (256 threads per block).
+static dim3 silu_grid(long n) {
+  long want = (n / 8 + 255) / 256;
+  return dim3((unsigned)(want < 4096 ? (want > 0 ? want : 1) : 4096));
+}
+
+// Grid of the gather kernels: one wave per row, 4 rows per 256-thread block.
+static dim3 gather_grid(int mb_size) { return dim3((mb_size + 3) / 4); }
 
 extern "C" void launch_bump_add(unsigned int* p, unsigned int n,
                                 void* stream) {
@@ -1061,33 +1134,17 @@ extern "C" void launch_policy_value_step(
     unsigned int draw_offset, int do_bump, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B + 15) / 16), block(256);
-  if (HID == 512) {
-    hipLaunchKernelGGL(policy_value_step_kernel<512>, grid, block, 0, s, obs,
-                       (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
-                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
-                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
-                       obs_mirror, action_out, logp_out, value_out, nmean,
-                       nvar, B, OBS, ACT, min_scale, aff_scale, aff_shift,
-                       log_aff_scale, greedy, seed, draw_buf, draw_offset);
-  } else if (HID == 256) {
-    hipLaunchKernelGGL(policy_value_step_kernel<256>, grid, block, 0, s, obs,
-                       (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
-                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
-                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
-                       obs_mirror, action_out, logp_out, value_out, nmean,
-                       nvar, B, OBS, ACT, min_scale, aff_scale, aff_shift,
-                       log_aff_scale, greedy, seed, draw_buf, draw_offset);
-  } else {
-    hipLaunchKernelGGL(policy_value_step_kernel<128>, grid, block, 0, s, obs,
-                       (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
-                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
-                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
-                       obs_mirror, action_out, logp_out, value_out, nmean,
-                       nvar, B, OBS, ACT, min_scale, aff_scale, aff_shift,
-                       log_aff_scale, greedy, seed, draw_buf, draw_offset);
-  }
-  if (draw_buf && do_bump)
-    hipLaunchKernelGGL(bump_u32_kernel2, dim3(1), dim3(1), 0, s, draw_buf);
+  dispatch_hid(HID, [&](auto hid) {
+    hipLaunchKernelGGL(policy_value_step_kernel<decltype(hid)::value>, grid,
+                       block, 0, s, obs, (const bf16_t*)W1a, b1a,
+                       (const bf16_t*)W2a, b2a, (const bf16_t*)Wha, bha,
+                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
+                       (const bf16_t*)Wvc, bvc, obs_mirror, action_out,
+                       logp_out, value_out, nmean, nvar, B, OBS, ACT,
+                       min_scale, aff_scale, aff_shift, log_aff_scale, greedy,
+                       seed, draw_buf, draw_offset);
+  });
+  bump_draw(draw_buf, do_bump, s);
 }
 
 extern "C" void launch_value_forward(const float* obs, const void* W1c,
@@ -1098,38 +1155,22 @@ extern "C" void launch_value_forward(const float* obs, const void* W1c,
                                      int B, int OBS, int HID, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B + 15) / 16), block(256);
-  if (HID == 512) {
-    hipLaunchKernelGGL(value_forward_kernel<512>, grid, block, 0, s, obs,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, value_out, nmean, nvar, B,
-                       OBS);
-  } else if (HID == 256) {
-    hipLaunchKernelGGL(value_forward_kernel<256>, grid, block, 0, s, obs,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, value_out, nmean, nvar, B,
-                       OBS);
-  } else {
-    hipLaunchKernelGGL(value_forward_kernel<128>, grid, block, 0, s, obs,
-                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
-                       (const bf16_t*)Wvc, bvc, value_out, nmean, nvar, B,
-                       OBS);
-  }
+  dispatch_hid(HID, [&](auto hid) {
+    hipLaunchKernelGGL(value_forward_kernel<decltype(hid)::value>, grid,
+                       block, 0, s, obs, (const bf16_t*)W1c, b1c,
+                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
+                       value_out, nmean, nvar, B, OBS);
+  });
 }
 
 extern "C" void launch_silu_fwd(const void* z, void* h, long n, void* stream) {
-  int threads = 256;
-  long want = (n / 8 + threads - 1) / threads;
-  int blocks = (int)(want < 4096 ? (want > 0 ? want : 1) : 4096);
-  hipLaunchKernelGGL(silu_fwd_kernel, dim3(blocks), dim3(threads), 0,
+  hipLaunchKernelGGL(silu_fwd_kernel, silu_grid(n), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)z, (bf16_t*)h, n);
 }
 
 extern "C" void launch_silu_bwd(const void* dh, const void* z, void* dz,
                                 long n, void* stream) {
-  int threads = 256;
-  long want = (n / 8 + threads - 1) / threads;
-  int blocks = (int)(want < 4096 ? (want > 0 ? want : 1) : 4096);
-  hipLaunchKernelGGL(silu_bwd_kernel, dim3(blocks), dim3(threads), 0,
+  hipLaunchKernelGGL(silu_bwd_kernel, silu_grid(n), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)dh, (const bf16_t*)z,
                      (bf16_t*)dz, n);
 }
@@ -1144,10 +1185,7 @@ extern "C" void launch_ppo_gather(const long* idx, int mb_size,
                                   float* adv_out, float* targets_out,
                                   const float* nmean, const float* nvar,
                                   void* stream) {
-  int threads = 256;
-  int rows_per_block = threads / 64;
-  int blocks = (mb_size + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(ppo_gather_kernel, dim3(blocks), dim3(threads), 0,
+  hipLaunchKernelGGL(ppo_gather_kernel, gather_grid(mb_size), dim3(256), 0,
                      (hipStream_t)stream, idx, mb_size, obs, OBS, OBS_PAD,
                      action, ACT, logp, value, adv, targets, (bf16_t*)obs_out,
                      action_out, logp_out, value_out, adv_out, targets_out,
@@ -1173,17 +1211,16 @@ extern "C" void launch_ppo_head_loss(
                      clip_eps, ent_coef,
                      vf_coef, min_scale, aff_scale, aff_shift, log_aff_scale,
                      1.0f / (float)B, seed, draw_buf, draw_offset);
-  if (draw_buf && do_bump)
-    hipLaunchKernelGGL(bump_u32_kernel2, dim3(1), dim3(1), 0, s, draw_buf);
+  bump_draw(draw_buf, do_bump, s);
 }
 
 // ===================================================================
 // Discrete (categorical) fused PPO path — BASELINE config #1 class
 // (discrete CartPole / MinAtar heads; reference heads.py:30-41
-// CategoricalHead). Same torso machinery as the tanh-normal kernels;
-// the epilogues differ: Gumbel-max sampling + log-softmax in the
-// rollout, exact categorical entropy + softmax-jacobian head backward
-// in the loss kernel. ACT <= 16 (one MFMA N-tile of logits).
+// CategoricalHead). Same forward as the tanh-normal kernels; the
+// epilogues differ: Gumbel-max sampling + log-softmax in the rollout,
+// exact categorical entropy + softmax-jacobian head backward in the loss
+// kernel. ACT <= 16 (one MFMA N-tile of logits).
 // ===================================================================
 
 template <int HID>
@@ -1209,43 +1246,15 @@ __launch_bounds__(256, 2) __global__ void policy_value_step_disc_kernel(
   const int rbase = blockIdx.x * 16;
   if (rbase >= B) return;
   const uint32_t draw = (draw_buf ? *draw_buf : 0u) + draw_offset;
-  const int K1P = (OBS + 31) & ~31;
 
-  bf16_t* O = &lds.O[0][0];
-  constexpr int OS = K1P_MAX + OPAD;
-  constexpr int HS = HID + HPAD;
-  bf16_t* Ha0 = &lds.H[0][0][0];
-  bf16_t* Ha1 = &lds.H[1][0][0];
-  bf16_t* Hc0 = &lds.H[2][0][0];
-  bf16_t* Hc1 = &lds.H[3][0][0];
-
-  stage_obs(obs, rbase, OBS, K1P, O, OS, nmean, nvar, obs_mirror,
-            threadIdx.x, 256, B);
-  __syncthreads();
-
-  wg_layer<HID, true>(O, OS, W1a, b1a, K1P, Ha0, HS, lane, wid);
-  wg_layer<HID, true>(O, OS, W1c, b1c, K1P, Hc0, HS, lane, wid);
-  __syncthreads();
-  wg_layer<HID, true>(Ha0, HS, W2a, b2a, HID, Ha1, HS, lane, wid);
-  wg_layer<HID, true>(Hc0, HS, W2c, b2c, HID, Hc1, HS, lane, wid);
-  __syncthreads();
-
-  if (wid == 1) {
-    wave_value_head<HID>(Hc1, HS, Wvc, bvc ? *bvc : 0.0f, rbase, value_out,
-                         lane, B);
-  }
+  actor_critic_forward<HID>(lds, obs, rbase, B, OBS, W1a, b1a, W2a, b2a, W1c,
+                            b1c, W2c, b2c, Wvc, bvc, nmean, nvar, obs_mirror,
+                            value_out, lane, wid);
 
   // ---- actor head: logits tile [16 rows x 16 cols] -> per-row
   // log-softmax + Gumbel-max sample (wave 0)
   if (wid == 0) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int arow = lane & 15, ak0 = (lane >> 4) * 8;
-    for (int ks = 0; ks < HID / 32; ++ks) {
-      const bf16x8 a =
-          *reinterpret_cast<const bf16x8*>(Ha1 + arow * HS + ks * 32 + ak0);
-      bf16x8 b = load_w_frag<HID>(Wha, HID, 0, ks, lane);
-      acc = MFMA_BF16_16x16x32(a, b, acc, 0, 0, 0);
-    }
+    f32x4 acc = head_tile<HID>(&lds.H[1][0][0], Wha, lane);
     const int col = lane & 15;
     const int g = lane >> 4;
     const bool valid = col < ACT;
@@ -1291,11 +1300,10 @@ __launch_bounds__(256, 2) __global__ void policy_value_step_disc_kernel(
   }
 }
 
-// Per-row categorical PPO head loss + analytic backward (see the
-// tanh-normal ppo_head_loss_kernel above for the shared clip/value math;
-// gradients here go through the softmax jacobian:
+// Categorical head: exact entropy; gradients go through the softmax
+// jacobian:
 // d logp_a / d logits_j = delta_aj - p_j;
-// dH / d logits_j = -p_j (logp_j + H)).
+// dH / d logits_j = -p_j (logp_j + H).
 extern "C" __global__ void ppo_head_loss_disc_kernel(
     const bf16_t* __restrict__ heads,    // [B, 16] logits (cols >= ACT pad)
     const bf16_t* __restrict__ v_in,     // [B]
@@ -1332,37 +1340,13 @@ extern "C" __global__ void ppo_head_loss_disc_kernel(
     logp_new = l[a] - lse;
   }
 
-  // ---- PPO clip loss (identical to the continuous kernel)
-  float A = active ? adv[row] : 0.0f;
-  float ratio = __expf(logp_new - (active ? old_logp[row] : 0.0f));
-  float r_clip = fmaxf(1.0f - clip_eps, fminf(1.0f + clip_eps, ratio));
-  float l1 = ratio * A, l2 = r_clip * A;
-  float a_loss = -fminf(l1, l2);
-  float dl_dlogp;
-  if (l1 <= l2) {
-    dl_dlogp = -ratio * A;
-  } else {
-    dl_dlogp = (ratio > 1.0f - clip_eps && ratio < 1.0f + clip_eps)
-                   ? -ratio * A
-                   : 0.0f;
-  }
-  dl_dlogp *= inv_B;
-
-  // ---- clipped value loss (identical)
-  float v_pred = active ? bf2f(v_in[row]) : 0.0f;
-  float ov = active ? old_value[row] : 0.0f;
-  float tg = active ? targets[row] : 0.0f;
-  float v_clip = ov + fmaxf(-clip_eps, fminf(clip_eps, v_pred - ov));
-  float e1 = (v_pred - tg), e2 = (v_clip - tg);
-  float sq1 = e1 * e1, sq2 = e2 * e2;
-  float v_loss = 0.5f * fmaxf(sq1, sq2);
-  float dv;
-  if (sq1 >= sq2) {
-    dv = e1;
-  } else {
-    dv = (fabsf(v_pred - ov) < clip_eps) ? e2 : 0.0f;
-  }
-  dv *= vf_coef * inv_B;
+  float dl_dlogp, dv;
+  float a_loss = ppo_clip_loss_row(logp_new, active ? old_logp[row] : 0.0f,
+                                   active ? adv[row] : 0.0f, clip_eps, inv_B,
+                                   &dl_dlogp);
+  float v_loss = clipped_value_loss_row(
+      active ? bf2f(v_in[row]) : 0.0f, active ? old_value[row] : 0.0f,
+      active ? targets[row] : 0.0f, clip_eps, vf_coef * inv_B, &dv);
 
   // ---- analytic logits gradient
   if (active) {
@@ -1385,25 +1369,10 @@ extern "C" __global__ void ppo_head_loss_disc_kernel(
     if (dv16_out) dv16_out[(long)row * 16] = f2bf(dv);
   }
 
-  if (metrics) {
-    float m0 = active ? a_loss * inv_B : 0.0f;
-    float m1 = active ? v_loss * inv_B : 0.0f;
-    float m2 = active ? Hent * inv_B : 0.0f;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      m0 += __shfl_down(m0, off);
-      m1 += __shfl_down(m1, off);
-      m2 += __shfl_down(m2, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&metrics[0], m0);
-      atomicAdd(&metrics[1], m1);
-      atomicAdd(&metrics[2], m2);
-    }
-  }
+  add_loss_metrics(metrics, active, a_loss, v_loss, Hent, inv_B);
 }
 
-// Minibatch gather for the discrete path: int64 actions, no per-dim loop.
+// Minibatch gather for the discrete path: one int64 action per row.
 extern "C" __global__ void ppo_gather_disc_kernel(
     const long* __restrict__ idx, int mb_size,
     const float* __restrict__ obs, int OBS, int OBS_PAD,
@@ -1414,28 +1383,11 @@ extern "C" __global__ void ppo_gather_disc_kernel(
     float* __restrict__ logp_out, float* __restrict__ value_out,
     float* __restrict__ adv_out, float* __restrict__ targets_out,
     const float* __restrict__ nmean, const float* __restrict__ nvar) {
-  int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int lane = threadIdx.x & 63;
-  if (row >= mb_size) return;
-  long src = idx[row];
-  for (int k = lane; k < OBS_PAD; k += 64) {
-    float v = 0.0f;
-    if (k < OBS) {
-      v = obs[src * OBS + k];
-      if (nmean) {
-        float sd = sqrtf(fmaxf(nvar[k], 1e-6f));
-        v = fmaxf(-10.0f, fminf(10.0f, (v - nmean[k]) / sd));
-      }
-    }
-    obs_out[(long)row * OBS_PAD + k] = f2bf(v);
-  }
-  if (lane == 0) {
-    action_out[row] = action[src];
-    logp_out[row] = logp[src];
-    value_out[row] = value[src];
-    adv_out[row] = adv[src];
-    targets_out[row] = targets[src];
-  }
+  ppo_gather_body(idx, mb_size, obs, OBS, OBS_PAD, logp, value, adv, targets,
+                  obs_out, logp_out, value_out, adv_out, targets_out, nmean,
+                  nvar, [=](long src, int row, int lane) {
+                    if (lane == 0) action_out[row] = action[src];
+                  });
 }
 
 extern "C" void launch_policy_value_step_disc(
@@ -1448,30 +1400,16 @@ extern "C" void launch_policy_value_step_disc(
     unsigned int draw_offset, int do_bump, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B + 15) / 16), block(256);
-  if (HID == 512) {
-    hipLaunchKernelGGL(policy_value_step_disc_kernel<512>, grid, block, 0, s,
-                       obs, (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
-                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
-                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
-                       obs_mirror, action_out, logp_out, value_out, nmean,
-                       nvar, B, OBS, ACT, greedy, seed, draw_buf, draw_offset);
-  } else if (HID == 256) {
-    hipLaunchKernelGGL(policy_value_step_disc_kernel<256>, grid, block, 0, s,
-                       obs, (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
-                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
-                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
-                       obs_mirror, action_out, logp_out, value_out, nmean,
-                       nvar, B, OBS, ACT, greedy, seed, draw_buf, draw_offset);
-  } else {
-    hipLaunchKernelGGL(policy_value_step_disc_kernel<128>, grid, block, 0, s,
-                       obs, (const bf16_t*)W1a, b1a, (const bf16_t*)W2a, b2a,
-                       (const bf16_t*)Wha, bha, (const bf16_t*)W1c, b1c,
-                       (const bf16_t*)W2c, b2c, (const bf16_t*)Wvc, bvc,
-                       obs_mirror, action_out, logp_out, value_out, nmean,
-                       nvar, B, OBS, ACT, greedy, seed, draw_buf, draw_offset);
-  }
-  if (draw_buf && do_bump)
-    hipLaunchKernelGGL(bump_u32_kernel2, dim3(1), dim3(1), 0, s, draw_buf);
+  dispatch_hid(HID, [&](auto hid) {
+    hipLaunchKernelGGL(policy_value_step_disc_kernel<decltype(hid)::value>,
+                       grid, block, 0, s, obs, (const bf16_t*)W1a, b1a,
+                       (const bf16_t*)W2a, b2a, (const bf16_t*)Wha, bha,
+                       (const bf16_t*)W1c, b1c, (const bf16_t*)W2c, b2c,
+                       (const bf16_t*)Wvc, bvc, obs_mirror, action_out,
+                       logp_out, value_out, nmean, nvar, B, OBS, ACT, greedy,
+                       seed, draw_buf, draw_offset);
+  });
+  bump_draw(draw_buf, do_bump, s);
 }
 
 extern "C" void launch_ppo_head_loss_disc(
@@ -1496,11 +1434,8 @@ extern "C" void launch_ppo_gather_disc(
     const float* adv, const float* targets, void* obs_out, long* action_out,
     float* logp_out, float* value_out, float* adv_out, float* targets_out,
     const float* nmean, const float* nvar, void* stream) {
-  int threads = 256;
-  int rows_per_block = threads / 64;
-  int blocks = (mb_size + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(ppo_gather_disc_kernel, dim3(blocks), dim3(threads), 0,
-                     (hipStream_t)stream, idx, mb_size, obs, OBS, OBS_PAD,
+  hipLaunchKernelGGL(ppo_gather_disc_kernel, gather_grid(mb_size), dim3(256),
+                     0, (hipStream_t)stream, idx, mb_size, obs, OBS, OBS_PAD,
                      action, logp, value, adv, targets, (bf16_t*)obs_out,
                      action_out, logp_out, value_out, adv_out, targets_out,
                      nmean, nvar);

@@ -540,6 +540,97 @@ def test_fused_rollout_megakernel_invariants(ext):
     assert torch.isfinite(learner.buf_bootstrap).all()
 
 
+ANT_MAX_STEPS = 1000
+
+
+def _rollout_step_ant_once(ext, H, ACT=8, truncate_rows=(), with_reference=True):
+    """One rollout_step_ant launch on B = 40 freshly reset Ant envs (two
+    full 16-row tiles plus one half tile), preceded (`with_reference`) by
+    policy_value_step on the same obs, weights, policy seed and draw
+    (counter 5 + offset 3). Rows in `truncate_rows` start one step short of
+    the episode limit."""
+    dev = "cuda"
+    B, OBS = 40, 27
+    # (weight, bias) pairs: weights go in as bf16 mirrors, biases stay fp32
+    w = [t.bfloat16() if i % 2 == 0 else t
+         for i, t in enumerate(_mk_weights(H, OBS, ACT, dev))]
+    state = torch.zeros(B, 29, device=dev)
+    ext.ant_reset(state, 77, 0)
+    # obs layout of ant_core.h ant_write_obs (pure copies of state columns)
+    obs = torch.cat([state[:, 2:3], state[:, 3:7], state[:, 13:21],
+                     state[:, 7:10], state[:, 10:13], state[:, 21:29]], 1).contiguous()
+    e = torch.zeros(0, device=dev)
+    f = lambda *s: torch.zeros(*s, device=dev)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    draw = torch.full((1,), 5, dtype=torch.int32, device=dev)
+    seed, off = 4321, 3
+    ref = dict(obs=f(B, OBS), action=f(B, ACT), logp=f(B), value=f(B))
+    if with_reference:
+        ext.policy_value_step(obs.clone(), *w, ref["obs"], ref["action"],
+                              ref["logp"], ref["value"], e, e, 1e-3, 1.0, 0.0,
+                              0.0, 0, seed, draw, off, 0)
+    step_count = i32(B)
+    step_count[list(truncate_rows)] = ANT_MAX_STEPS - 1
+    out = dict(obs=f(B, OBS), action=f(B, ACT), logp=f(B), value=f(B),
+               bootstrap=torch.full((B,), float("nan"), device=dev),
+               reward=f(B), discount=f(B),
+               steptype=torch.zeros(B, dtype=torch.uint8, device=dev))
+    ext.rollout_step_ant(
+        obs.clone(), state, step_count, f(B), i32(B), f(B), i32(B), *w,
+        out["obs"], out["action"], out["logp"], out["value"], out["bootstrap"],
+        out["reward"], out["discount"], out["steptype"], ANT_MAX_STEPS, 1e-3,
+        1.0, 0.0, 0.0, seed, 99, draw, i32(1), off)
+    torch.cuda.synchronize()
+    assert draw.item() == 5  # neither call bumps the counter
+    return ref, out
+
+
+@requires_gpu
+@pytest.mark.parametrize("H", [128, 256, 512])
+def test_rollout_step_ant_matches_policy_value_step(ext, H):
+    """The megakernel and policy_value_step share one forward and one
+    sampling epilogue: same inputs, seed and draw give bit-equal obs
+    mirror, action, log-prob and value at every instantiated width."""
+    ref, out = _rollout_step_ant_once(ext, H)
+    for k in ("obs", "action", "logp", "value"):
+        assert torch.equal(out[k], ref[k]), k
+
+
+@requires_gpu
+@pytest.mark.parametrize("H", [128, 256, 512])
+def test_rollout_step_ant_bootstrap_only_on_done_rows(ext, H):
+    """The bootstrap critic pass stores V(next_obs) for done rows only (the
+    row mask handed to the shared value head): rows 1, 17 and 39 truncate,
+    one in each tile, and every row that did not end keeps its NaN fill."""
+    rows = (1, 17, 39)
+    _, out = _rollout_step_ant_once(ext, H, truncate_rows=rows)
+    done = out["steptype"] >= 2
+    assert done[list(rows)].all()
+    assert not done.all()
+    assert torch.isfinite(out["bootstrap"][done]).all()
+    assert torch.isnan(out["bootstrap"][~done]).all()
+
+
+@requires_gpu
+def test_fused_mlp_rejects_unsupported_shapes(ext):
+    """Widths and head sizes no kernel is instantiated for raise before any
+    launch instead of running a kernel of another shape."""
+    dev = "cuda"
+    B, OBS = 40, 27
+    w = _mk_weights(64, OBS, 8, dev)
+    bf = lambda t: t.bfloat16()
+    e = torch.zeros(0, device=dev)
+    obs, v = torch.zeros(B, OBS, device=dev), torch.zeros(B, device=dev)
+    with pytest.raises(RuntimeError, match="HID 128/256/512, got 64"):
+        ext.value_forward(obs, bf(w[6]), w[7], bf(w[8]), w[9], bf(w[10]),
+                          w[11], v, e, e)
+    # the messages come from the rollout_step_ant wrapper alone
+    with pytest.raises(RuntimeError, match="HID 128/256/512, got 64"):
+        _rollout_step_ant_once(ext, 64, with_reference=False)
+    with pytest.raises(RuntimeError, match="rollout_step_ant needs OBS == 27 and ACT == 8"):
+        _rollout_step_ant_once(ext, 128, ACT=4, with_reference=False)
+
+
 @requires_gpu
 @pytest.mark.parametrize("K", [32, 256])
 def test_linear_silu_kernel_matches_torch(ext, K):
