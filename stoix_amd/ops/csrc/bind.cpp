@@ -67,6 +67,10 @@ void launch_linear_silu(const void*, const void*, const float*, void*,
                         void*, int, int, int, int, void*);
 void launch_silu_fwd(const void*, void*, long, void*);
 void launch_silu_bwd(const void*, const void*, void*, long, void*);
+void launch_silu_heads_fwd(const void*, const void*, const void*, const void*,
+                           const void*, void*, void*, void*, int, int, void*);
+void launch_heads_bwd_silu(const void*, const void*, const void*, const void*,
+                           const void*, void*, int, int, void*);
 void launch_ppo_gather(const long*, int, const float*, int, int,
                        const float*, int,
                        const float*, const float*, const float*, const float*,
@@ -527,6 +531,60 @@ void silu_bwd(torch::Tensor dh, torch::Tensor z, torch::Tensor dz) {
                   cur_stream());
 }
 
+// Shape checks shared by the two fused head kernels over the stacked
+// [2, S, HID] buffers. `rows1` may be empty where it is optional. Returns
+// S; HID comes back through `hid`.
+int check_stacked_heads(const torch::Tensor& Z2, const torch::Tensor& other,
+                        const torch::Tensor& Wh, const torch::Tensor& Wv,
+                        const torch::Tensor& rows16, const torch::Tensor& rows1,
+                        bool rows1_optional, int* hid) {
+  CHK(Z2, torch::kBFloat16);
+  CHK(other, torch::kBFloat16);
+  CHK(rows16, torch::kBFloat16);
+  CHK(rows1, torch::kBFloat16);
+  TORCH_CHECK(Z2.dim() == 3 && Z2.size(0) == 2,
+              "fused heads need stacked [2, S, HID] buffers");
+  const int64_t S = Z2.size(1), HID = Z2.size(2);
+  TORCH_CHECK(HID == 512 || HID == 256 || HID == 128,
+              "fused heads support HID 128/256/512, got ", HID);
+  TORCH_CHECK(S % 16 == 0, "fused heads need S % 16 == 0, got ", S);
+  TORCH_CHECK(other.sizes() == Z2.sizes(),
+              "fused heads: [2, S, HID] buffers differ in shape");
+  check_fused_weight(Wh, "Wh", 16, HID);
+  check_fused_weight(Wv.view({-1, 1}), "Wv", HID, 1);
+  TORCH_CHECK(rows16.numel() == S * 16, "fused heads: expected [S, 16]");
+  TORCH_CHECK(rows1.numel() == S || (rows1_optional && rows1.numel() == 0),
+              "fused heads: expected [S]");
+  *hid = (int)HID;
+  return (int)S;
+}
+
+void silu_heads_fwd(torch::Tensor Z2, torch::Tensor Wh, torch::Tensor bh,
+                    torch::Tensor Wv, torch::Tensor bv, torch::Tensor H2,
+                    torch::Tensor heads, torch::Tensor vpred) {
+  int HID;
+  // an empty vpred leaves the value head to the caller (critic: silu only)
+  int S = check_stacked_heads(Z2, H2, Wh, Wv, heads, vpred, true, &HID);
+  CHK(bh, torch::kBFloat16);
+  CHK(bv, torch::kBFloat16);
+  TORCH_CHECK(bh.numel() == 16 && bv.numel() == 1,
+              "silu_heads_fwd: bh must be [16] and bv [1]");
+  launch_silu_heads_fwd(Z2.data_ptr(), Wh.data_ptr(), bh.data_ptr(),
+                        Wv.data_ptr(), bv.data_ptr(), H2.data_ptr(),
+                        heads.data_ptr(),
+                        vpred.numel() > 0 ? vpred.data_ptr() : nullptr, S,
+                        HID, cur_stream());
+}
+
+void heads_bwd_silu(torch::Tensor dhead, torch::Tensor dv, torch::Tensor Wh,
+                    torch::Tensor Wv, torch::Tensor Z2, torch::Tensor dZ2) {
+  int HID;
+  int S = check_stacked_heads(Z2, dZ2, Wh, Wv, dhead, dv, false, &HID);
+  launch_heads_bwd_silu(dhead.data_ptr(), dv.data_ptr(), Wh.data_ptr(),
+                        Wv.data_ptr(), Z2.data_ptr(), dZ2.data_ptr(), S, HID,
+                        cur_stream());
+}
+
 void ppo_gather(torch::Tensor idx, torch::Tensor obs, torch::Tensor action,
                 torch::Tensor logp, torch::Tensor value, torch::Tensor adv,
                 torch::Tensor targets, torch::Tensor obs_out,
@@ -729,6 +787,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused Linear(+bias)+SiLU forward, MFMA tiled");
   m.def("silu_fwd", &silu_fwd, "bf16 silu forward");
   m.def("silu_bwd", &silu_bwd, "bf16 silu backward");
+  m.def("silu_heads_fwd", &silu_heads_fwd,
+        "stacked silu forward fused with the actor/critic head GEMMs");
+  m.def("heads_bwd_silu", &heads_bwd_silu,
+        "head dgrads (K=16 / K=1) fused with the stacked silu backward");
   m.def("ppo_gather", &ppo_gather, "fused minibatch gather");
   m.def("ppo_head_loss", &ppo_head_loss,
         "fused PPO head fwd + losses + analytic head bwd");

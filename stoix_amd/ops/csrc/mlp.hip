@@ -16,7 +16,10 @@
 //     per sample row);
 //   * linear_silu, silu fwd/bwd + gather kernels: the epilogue/prologue
 //     glue so the update phase is GEMM (hipBLASLt MFMA) + a handful of
-//     fused kernels.
+//     fused kernels;
+//   * silu_heads_fwd / heads_bwd_silu: the layer-2 SiLU passes of the
+//     update with the narrow head GEMMs (N=16/1 forward, K=16/1 backward)
+//     formed from the tile the pass already holds.
 //
 // Geometry (forward kernels): one workgroup of 4 waves owns ONE 16-row
 // batch tile. Each layer's N (HID columns) is split across the waves: wave
@@ -831,6 +834,255 @@ extern "C" __global__ void silu_bwd_kernel(const bf16_t* __restrict__ dh,
   }
 }
 
+// ------------------------------- SiLU fused with the PPO head GEMMs (update)
+//
+// silu_heads_fwd: H2 = silu(Z2) and both head projections in the pass that
+// produces H2 (the separate head GEMMs re-read H2 to produce 1 MB).
+// heads_bwd_silu: dZ2 = (dhead @ Wh | dv * Wv) * silu'(Z2) without the bf16
+// dH2 round trip through memory. Both run over the stacked [2, S, HID]
+// buffers, net 0 = actor, net 1 = critic (blockIdx.y).
+//
+// Geometry: one WAVE owns one 16-row tile, 4 tiles per workgroup. Every
+// access to an [S, HID] stream is 16 B per lane along the row (a tile is
+// 16*HID contiguous elements: instruction i, lane l moves elements
+// i*512 + l*8 ..+8). The MFMA fragment layouts are reached through a
+// wave-private padded LDS tile. The head weights are staged in LDS once per
+// workgroup; the barrier after the staging is the only one, every wave
+// reaches it, and a wave with no tile leaves only after it.
+
+// Orders a wave's LDS stores before its later LDS loads (other lanes' data)
+// for the compiler; the hardware runs one wave's LDS operations in order.
+DEV_INLINE void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+DEV_INLINE bf16x8 zero_bf16x8() {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = f2bf(0.0f);
+  return v;
+}
+
+template <int HID>
+struct HeadsFwdLds {
+  static constexpr int HS = HID + HPAD;
+  alignas(16) bf16_t W[16][HS];         // Wh, or Wv in row 0 and zeros below
+  alignas(16) bf16_t T[4][16][HS];      // per-wave silu(Z2) tile
+  alignas(16) bf16_t O[4][16][16 + HPAD];  // per-wave head tile
+};
+
+template <int HID>
+__launch_bounds__(256) __global__ void silu_heads_fwd_kernel(
+    const bf16_t* __restrict__ Z2,   // [2, S, HID]
+    const bf16_t* __restrict__ Wh,   // [16, HID]
+    const bf16_t* __restrict__ bh,   // [16] bf16 mirror
+    const bf16_t* __restrict__ Wv,   // [HID]
+    const bf16_t* __restrict__ bv,   // [1] bf16 mirror
+    bf16_t* __restrict__ H2,         // [2, S, HID]
+    bf16_t* __restrict__ heads,      // [S, 16]
+    bf16_t* __restrict__ vpred,      // [S], or null: critic tiles only silu
+    int S) {
+  __shared__ HeadsFwdLds<HID> lds;
+  constexpr int CPR = HID / 8;   // 16-B chunks per row
+  constexpr int RPI = 64 / CPR;  // rows per wave instruction
+  constexpr int NIT = HID / 32;  // wave instructions per tile
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int net = blockIdx.y;
+
+  // B operand: the actor's Wh, or the critic's Wv as a 1-row tile
+  for (int c = threadIdx.x; c < 16 * CPR; c += 256) {
+    const int n = c / CPR, k8 = (c % CPR) * 8;
+    bf16x8 w = zero_bf16x8();
+    if (net == 0)
+      w = *reinterpret_cast<const bf16x8*>(Wh + n * HID + k8);
+    else if (n == 0)
+      w = *reinterpret_cast<const bf16x8*>(Wv + k8);
+    *reinterpret_cast<bf16x8*>(&lds.W[n][k8]) = w;
+  }
+  __syncthreads();
+
+  const int rbase = (blockIdx.x * 4 + wid) * 16;
+  if (rbase >= S) return;
+  const long base = ((long)net * S + rbase) * HID;
+  const bf16_t* zt = Z2 + base;
+  bf16_t* ht = H2 + base;
+  const int lrow = lane / CPR, lcol = (lane % CPR) * 8;
+
+  bf16x8 zv[NIT];
+#pragma unroll
+  for (int i = 0; i < NIT; ++i)
+    zv[i] = *reinterpret_cast<const bf16x8*>(zt + i * 512 + lane * 8);
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) {
+    bf16x8 hv;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) hv[j] = f2bf(silu_f(bf2f(zv[i][j])));
+    *reinterpret_cast<bf16x8*>(ht + i * 512 + lane * 8) = hv;
+    *reinterpret_cast<bf16x8*>(&lds.T[wid][i * RPI + lrow][lcol]) = hv;
+  }
+  if (net == 1 && vpred == nullptr) return;  // value head left to the caller
+  wave_lds_sync();
+
+  // head tile: the fragment conventions of head_tile, both operands in LDS
+  const int col = lane & 15, g = lane >> 4;
+  // the bf16 mirror bias, fetched ahead of the MFMA chain so that nothing
+  // but straight-line code sits between the last MFMA and the use of acc
+  const float bias_raw = bf2f(net == 0 ? bh[col] : bv[0]);
+  const float bias = (net == 0 || col == 0) ? bias_raw : 0.0f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < NIT; ++ks) {
+    const bf16x8 a =
+        *reinterpret_cast<const bf16x8*>(&lds.T[wid][col][ks * 32 + g * 8]);
+    const bf16x8 b =
+        *reinterpret_cast<const bf16x8*>(&lds.W[col][ks * 32 + g * 8]);
+    acc = MFMA_BF16_16x16x32(a, b, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lds.O[wid][g * 4 + r][col] = f2bf(acc[r] + bias);
+  wave_lds_sync();
+  if (net == 0) {
+    if (lane < 32) {
+      const int row = lane >> 1, half = (lane & 1) * 8;
+      *reinterpret_cast<bf16x8*>(heads + (long)(rbase + row) * 16 + half) =
+          *reinterpret_cast<const bf16x8*>(&lds.O[wid][row][half]);
+    }
+  } else if (lane < 16) {
+    vpred[rbase + lane] = lds.O[wid][lane][0];
+  }
+}
+
+template <int HID>
+struct HeadsBwdLds {
+  static constexpr int HS = HID + HPAD;
+  alignas(16) bf16_t WT[HID][16 + HPAD];  // Wh transposed: [column][head]
+  alignas(16) bf16_t Q[4][16][HS];        // per-wave dH2 tile
+};
+
+template <int HID>
+__launch_bounds__(256) __global__ void heads_bwd_silu_kernel(
+    const bf16_t* __restrict__ dhead,  // [S, 16]
+    const bf16_t* __restrict__ dv,     // [S]
+    const bf16_t* __restrict__ Wh,     // [16, HID]
+    const bf16_t* __restrict__ Wv,     // [HID]
+    const bf16_t* __restrict__ Z2,     // [2, S, HID]
+    bf16_t* __restrict__ dZ2,          // [2, S, HID]
+    int S) {
+  __shared__ HeadsBwdLds<HID> lds;
+  constexpr int CPR = HID / 8;
+  constexpr int RPI = 64 / CPR;
+  constexpr int NIT = HID / 32;
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int net = blockIdx.y;
+
+  if (net == 0) {
+    for (int c = threadIdx.x; c < 16 * CPR; c += 256) {
+      const int n = c / CPR, k8 = (c % CPR) * 8;
+      const bf16x8 w = *reinterpret_cast<const bf16x8*>(Wh + n * HID + k8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) lds.WT[k8 + j][n] = w[j];
+    }
+  }
+  __syncthreads();
+
+  const int rbase = (blockIdx.x * 4 + wid) * 16;
+  if (rbase >= S) return;
+  const long base = ((long)net * S + rbase) * HID;
+  const bf16_t* zt = Z2 + base;
+  bf16_t* dzt = dZ2 + base;
+  const int lrow = lane / CPR, lcol = (lane % CPR) * 8;
+
+  bf16x8 zv[NIT];
+#pragma unroll
+  for (int i = 0; i < NIT; ++i)
+    zv[i] = *reinterpret_cast<const bf16x8*>(zt + i * 512 + lane * 8);
+
+  if (net == 1) {
+    // rank-1 critic half: dH2 = dv * Wv, one product per element
+    const bf16x8 wv = *reinterpret_cast<const bf16x8*>(Wv + lcol);
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const float d = bf2f(dv[rbase + i * RPI + lrow]);
+      bf16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bf16_t q = f2bf(d * bf2f(wv[j]));
+        o[j] = f2bf(bf2f(q) * silu_grad_f(bf2f(zv[i][j])));
+      }
+      *reinterpret_cast<bf16x8*>(dzt + i * 512 + lane * 8) = o;
+    }
+    return;
+  }
+
+  // actor half, transposed so that a lane ends up with 8 adjacent columns
+  // of one row: D = WT-rows x dhead^T, K = 16 heads in the lower K half
+  // (lanes 32..63 hold the zero upper half of both operands). A-row m of
+  // MFMA p of 32-column block b is column b*32 + (m>>2)*8 + p*4 + (m&3),
+  // so lane l gets columns b*32 + (l>>4)*8 + p*4 + r of row l&15.
+  const int m = lane & 15, g = lane >> 4;
+  bf16x8 dh = *reinterpret_cast<const bf16x8*>(dhead + (long)(rbase + m) * 16 +
+                                               (g & 1) * 8);
+  if (g >= 2) dh = zero_bf16x8();
+#pragma unroll
+  for (int b = 0; b < NIT; ++b) {
+    bf16x8 q;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int c = b * 32 + (m >> 2) * 8 + p * 4 + (m & 3);
+      bf16x8 a = *reinterpret_cast<const bf16x8*>(&lds.WT[c][(g & 1) * 8]);
+      if (g >= 2) a = zero_bf16x8();
+      f32x4 d = {0.f, 0.f, 0.f, 0.f};
+      d = MFMA_BF16_16x16x32(a, dh, d, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) q[p * 4 + r] = f2bf(d[r]);
+    }
+    *reinterpret_cast<bf16x8*>(&lds.Q[wid][m][b * 32 + g * 8]) = q;
+  }
+  wave_lds_sync();
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) {
+    const bf16x8 q =
+        *reinterpret_cast<const bf16x8*>(&lds.Q[wid][i * RPI + lrow][lcol]);
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      o[j] = f2bf(bf2f(q[j]) * silu_grad_f(bf2f(zv[i][j])));
+    *reinterpret_cast<bf16x8*>(dzt + i * 512 + lane * 8) = o;
+  }
+}
+
+// S % 16 == 0 (whole tiles) and HID are checked by the callers in bind.cpp.
+extern "C" void launch_silu_heads_fwd(const void* Z2, const void* Wh,
+                                      const void* bh, const void* Wv,
+                                      const void* bv, void* H2, void* heads,
+                                      void* vpred, int S, int HID,
+                                      void* stream) {
+  dim3 grid((S / 16 + 3) / 4, 2), block(256);
+  dispatch_hid(HID, [&](auto hid) {
+    hipLaunchKernelGGL(silu_heads_fwd_kernel<decltype(hid)::value>, grid,
+                       block, 0, (hipStream_t)stream, (const bf16_t*)Z2,
+                       (const bf16_t*)Wh, (const bf16_t*)bh,
+                       (const bf16_t*)Wv, (const bf16_t*)bv, (bf16_t*)H2,
+                       (bf16_t*)heads, (bf16_t*)vpred, S);
+  });
+}
+
+extern "C" void launch_heads_bwd_silu(const void* dhead, const void* dv,
+                                      const void* Wh, const void* Wv,
+                                      const void* Z2, void* dZ2, int S,
+                                      int HID, void* stream) {
+  dim3 grid((S / 16 + 3) / 4, 2), block(256);
+  dispatch_hid(HID, [&](auto hid) {
+    hipLaunchKernelGGL(heads_bwd_silu_kernel<decltype(hid)::value>, grid,
+                       block, 0, (hipStream_t)stream, (const bf16_t*)dhead,
+                       (const bf16_t*)dv, (const bf16_t*)Wh,
+                       (const bf16_t*)Wv, (const bf16_t*)Z2, (bf16_t*)dZ2, S);
+  });
+}
+
 // Fused minibatch gather: one kernel replaces 6 index_selects. Gathers the
 // permuted rows of the flat rollout storage for one minibatch (obs -> bf16
 // GEMM input, normalised if asked; the scalar fields fp32). One wave per
@@ -889,14 +1141,14 @@ extern "C" __global__ void ppo_gather_kernel(
 
 // ---------------------------------------------- fused PPO head + losses
 //
-// One THREAD per sample row. The head projections themselves are GEMMs and
-// run on hipBLASLt in the engine (heads = H2a @ Wha^T + bha -> [B,16],
-// v = H2c @ Wvc + bvc -> [B]); the head-loss kernels do the remaining
+// One THREAD per sample row. The head projections themselves (heads =
+// H2a @ Wha^T + bha -> [B,16], v = H2c @ Wvc + bvc -> [B]) come from
+// silu_heads_fwd above; the head-loss kernels do the remaining
 // per-row scalar math: log-prob of the stored action, PPO clip loss
 // (losses.py ppo_clip_loss), clipped value loss, entropy, and the analytic
 // gradients d(total)/d{head outputs, v} (verified against autograd in
-// tests/test_fused_math.py). dH2a/dH2c are then GEMMs again (dhead @ Wha,
-// dv @ Wvc) in the engine.
+// tests/test_fused_math.py). dH2a/dH2c (dhead @ Wha, dv @ Wvc) are then
+// formed inside heads_bwd_silu.
 //
 // Gradient scale: total = a_loss - ent_coef*entropy + vf_coef*v_loss,
 // all means over the minibatch (inv_B folded in here). The clip loss, the

@@ -14,11 +14,13 @@ stoix_amd/ops/csrc/mlp.hip:
                  non-Ant HIP envs
   minibatch:     ppo_gather -> layer-1 fused linear_silu per net (custom
                  MFMA wins at K=32) -> layer-2 tuned hipBLASLt GemmAndBias
-                 per net + ONE stacked silu (library wins at K=256)
-                 -> head GEMMs -> ppo_head_loss (per-row losses + analytic
+                 per net (library wins at K=256) -> silu_heads_fwd (ONE
+                 stacked silu that also forms both heads from the tile it
+                 holds) -> ppo_head_loss (per-row losses + analytic
                  head bwd; metrics only on the reported minibatch)
-                 -> stacked backward over [2, S, H] buffers: one silu_bwd
-                 per layer pair, dH1 as one batched bmm against the
+                 -> stacked backward over [2, S, H] buffers: heads_bwd_silu
+                 (head dgrads formed inside the layer-2 silu backward),
+                 one silu_bwd for layer 1, dH1 as one batched bmm against the
                  adjacent-W2 [2, H, H] view, split-K wgrads into per-chain
                  slabs -> slab_reduce per chain
                  -> ONE bf16 RCCL all-reduce over both chains' shared
@@ -354,6 +356,18 @@ class FusedPPOEngine:
 
         # batched dH1 GEMM (one bmm vs two mm); A/B knob for measurement
         self.use_bmm = _os.environ.get("STOIX_FUSED_BMM", "1") != "0"
+        # silu fused with the head GEMMs (silu_heads_fwd / heads_bwd_silu);
+        # "0" restores the silu + hipBLASLt head GEMM sequence (A/B knob).
+        # The value head stays on hipBLASLt by default: at S=32768 its
+        # gemv-like kernel sums in another order than the MFMA k order, a
+        # few vpred elements per minibatch differ by one bf16 ulp, and 192
+        # Adam steps turn that into visibly different parameters. "2" fuses
+        # it too (measured 24.3 vs 25.3 ms/step, results not bit-equal to
+        # the GEMM sequence; profiles/ppo_ant_fused_heads_SUMMARY.md).
+        _heads = _os.environ.get("STOIX_FUSED_HEADS", "1")
+        self.fused_heads = _heads != "0"
+        self.fused_vpred = _heads == "2"
+        self.no_vpred = z(0)
         # side-stream gather prefetch. Measured SLOWER (28.0 vs 26.8
         # ms/step): the backward kernels already fill all 256 CUs, so the
         # concurrent gather steals bandwidth instead of hiding latency.
@@ -615,12 +629,26 @@ class FusedPPOEngine:
             ext.linear_silu(w.Xmb, c16["W1"], cc.views["b1"], self.Z1[1], self.H1[1], 1)
             torch.addmm(a16["b2"], self.H1[0], a16["W2"].t(), out=self.Z2[0])
             torch.addmm(c16["b2"], self.H1[1], c16["W2"].t(), out=self.Z2[1])
-            ext.silu_fwd(self.Z2, self.H2)
-            # ---- heads as GEMMs (hipBLASLt), then the fused per-row
-            # loss + analytic head-backward kernel, then dH2 as GEMMs
-            torch.addmm(a16["bh"], self.H2[0], a16["Wh"].t(), out=self.heads)
-            torch.addmm(c16["bv"], self.H2[1], c16["Wv"].view(self.H, 1),
-                        out=self.vpred)
+            # ---- silu + the actor head in one pass over Z2 (the N=16 head
+            # GEMM is a re-read of H2[0]); the N=1 value head stays a
+            # hipBLASLt GEMM unless the knob asks for it too (see
+            # __init__). Then the fused per-row loss + analytic
+            # head-backward kernel. Knob off: silu, then both heads as
+            # hipBLASLt GEMMs.
+            if self.fused_heads:
+                ext.silu_heads_fwd(
+                    self.Z2, a16["Wh"], a16["bh"], c16["Wv"], c16["bv"],
+                    self.H2, self.heads,
+                    self.vpred if self.fused_vpred else self.no_vpred)
+                if not self.fused_vpred:
+                    torch.addmm(c16["bv"], self.H2[1],
+                                c16["Wv"].view(self.H, 1), out=self.vpred)
+            else:
+                ext.silu_fwd(self.Z2, self.H2)
+                torch.addmm(a16["bh"], self.H2[0], a16["Wh"].t(),
+                            out=self.heads)
+                torch.addmm(c16["bv"], self.H2[1], c16["Wv"].view(self.H, 1),
+                            out=self.vpred)
             # metrics only on the LAST minibatch (the one epoch() reports):
             # 512 waves of atomics into 3 words serialise across XCDs
             last = mb == n_mb - 1
@@ -642,18 +670,26 @@ class FusedPPOEngine:
                     self.vf_coef, self.min_scale, self.aff_scale, self.aff_shift,
                     self.log_aff_scale, self.seed, self.draw_ent, mb, 0,
                 )
-            torch.mm(self.dhead, a16["Wh"], out=self.dH2[0])
-            torch.mm(self.dv, c16["Wv"].view(1, self.H), out=self.dH2[1])
+            if not self.fused_heads:
+                torch.mm(self.dhead, a16["Wh"], out=self.dH2[0])
+                torch.mm(self.dv, c16["Wv"].view(1, self.H), out=self.dH2[1])
             # ---- backward: wgrads + bias colsums via the split-K MFMA
             # wgrad kernel (wgrad.hip; hipBLASLt NT at K=32768 is ~3x
             # slower), partial sums land in the chain slab, one
             # slab_reduce per chain folds them into the flat bf16 grads.
-            # silu_bwd runs once over the stacked [2, S, H] buffers and the
-            # two dH1 GEMMs go as one bmm against the adjacent-W2 view.
+            # The K=16 / K=1 head dgrads are formed inside the layer-2
+            # silu backward (dH2 stays on chip; knob off: dH2 as GEMMs,
+            # then silu_bwd); the layer-1 silu_bwd runs once over the
+            # stacked [2, S, H] buffers and the two dH1 GEMMs go as one
+            # bmm against the adjacent-W2 view.
             ao, co = ac.offsets, cc.offsets
             ext.wgrad(self.dhead, self.H2[0], ac.slab, ao["Wh"], ao["bh"], 16)
             ext.wgrad(self.dv16, self.H2[1], cc.slab, co["Wv"], co["bv"], 1)
-            ext.silu_bwd(self.dH2, self.Z2, self.dZ2)
+            if self.fused_heads:
+                ext.heads_bwd_silu(self.dhead, self.dv, a16["Wh"], c16["Wv"],
+                                   self.Z2, self.dZ2)
+            else:
+                ext.silu_bwd(self.dH2, self.Z2, self.dZ2)
             ext.wgrad(self.dZ2[0], self.H1[0], ac.slab, ao["W2"], ao["b2"], self.H)
             ext.wgrad(self.dZ2[1], self.H1[1], cc.slab, co["W2"], co["b2"], self.H)
             if self.use_bmm:

@@ -126,6 +126,23 @@ def main():
     def k_headgemm():
         torch.addmm(a16["bh"], F.H2[0], a16["Wh"].t(), out=F.heads)
 
+    def k_silu_stacked():
+        ext.silu_fwd(F.Z2, F.H2)
+
+    def k_vgemm():
+        torch.addmm(c16["bv"], F.H2[1], c16["Wv"].view(F.H, 1), out=F.vpred)
+
+    def k_silu_heads_fwd():
+        ext.silu_heads_fwd(F.Z2, a16["Wh"], a16["bh"], c16["Wv"], c16["bv"],
+                           F.H2, F.heads, F.vpred)
+
+    def k_head_dgrads():
+        torch.mm(F.dhead, a16["Wh"], out=F.dH2[0])
+        torch.mm(F.dv, c16["Wv"].view(1, F.H), out=F.dH2[1])
+
+    def k_heads_bwd_silu():
+        ext.heads_bwd_silu(F.dhead, F.dv, a16["Wh"], c16["Wv"], F.Z2, F.dZ2)
+
     def k_head():
         F.metrics.zero_()
         ext.ppo_head_loss(
@@ -166,13 +183,20 @@ def main():
     print(f"silu_fwd:           {timeit(k_silu, 50)*1e3:8.1f} us")
     print(f"linear_silu fused:  {timeit(k_linsilu, 50)*1e3:8.1f} us")
     print(f"head gemm:          {timeit(k_headgemm, 50)*1e3:8.1f} us")
+    print(f"value gemm:         {timeit(k_vgemm, 50)*1e3:8.1f} us")
+    print(f"silu_fwd stacked:   {timeit(k_silu_stacked, 50)*1e3:8.1f} us")
+    print(f"silu_heads_fwd:     {timeit(k_silu_heads_fwd, 50)*1e3:8.1f} us"
+          "  (replaces the three above)")
     print(f"ppo_head_loss:      {timeit(k_head, 50)*1e3:8.1f} us")
     print(f"wgrad mm:           {timeit(k_wgrad, 50)*1e3:8.1f} us")
     print(f"wgrad custom:       {timeit(k_wgrad_custom, 50)*1e3:8.1f} us")
     print(f"slab_reduce:        {timeit(k_slab_reduce, 50)*1e3:8.1f} us")
     print(f"dgrad mm:           {timeit(k_dgrad, 50)*1e3:8.1f} us")
     print(f"dgrad bmm stacked:  {timeit(k_dgrad_bmm, 50)*1e3:8.1f} us")
+    print(f"head dgrads (2 mm): {timeit(k_head_dgrads, 50)*1e3:8.1f} us")
     print(f"silu_bwd stacked:   {timeit(k_silu_bwd_stacked, 50)*1e3:8.1f} us")
+    print(f"heads_bwd_silu:     {timeit(k_heads_bwd_silu, 50)*1e3:8.1f} us"
+          "  (replaces the two above)")
     print(f"bias colsum:        {timeit(k_bsum, 50)*1e3:8.1f} us")
     print(f"fused_adam_bf16:    {timeit(k_adam, 50)*1e3:8.1f} us")
 
