@@ -24,6 +24,7 @@ SOURCES = [
     str(CSRC / "per.hip"),
     str(CSRC / "rnn.hip"),
     str(CSRC / "snake.hip"),
+    str(CSRC / "c51.hip"),
 ]
 
 

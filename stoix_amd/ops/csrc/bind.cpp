@@ -116,6 +116,13 @@ void launch_snake_step(int*, long*, long*, long*, long*, int*, const long*,
                        float*, float*, unsigned char*, unsigned char*, int,
                        int, uint64_t, unsigned int*, unsigned int, int,
                        void*);
+void launch_c51_loss_fwd(const void*, const float*, const long*, const float*,
+                         const float*, const void*, const float*,
+                         const float*, float*, float*, float*, int, int, int,
+                         int, int, int, long, long, long, void*);
+void launch_c51_loss_bwd(const float*, long, const void*, const long*,
+                         const float*, const float*, void*, int, int, int,
+                         int, long, void*);
 }
 
 namespace {
@@ -672,6 +679,109 @@ void tr16_probe(torch::Tensor in, torch::Tensor out, int64_t base_mode) {
                     cur_stream());
 }
 
+// Argument checks shared by the two C51 loss launchers (c51.hip): logits are
+// contiguous fp32 or bf16 [B, A, atoms] with 1 <= A <= 64 and
+// 1 <= atoms <= 1024; the action vector is int64 [B], or empty for A == 1.
+// Per-row vectors (a_tm1, r_t, d_t, grad_ce) may be strided views, e.g. a
+// column of a batch or an expanded scalar. Returns 1 for bf16 logits.
+int check_c51_logits(const torch::Tensor& logits, const char* name,
+                     int64_t B, int64_t A) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous(), name,
+              " must be a contiguous GPU tensor");
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32 ||
+                  logits.scalar_type() == torch::kBFloat16,
+              name, " must be fp32 or bf16");
+  TORCH_CHECK(logits.dim() == 3 && logits.size(0) == B && logits.size(1) == A,
+              name, " must be [", B, ", ", A, ", atoms]");
+  TORCH_CHECK(A >= 1 && A <= 64, "c51 loss supports 1 <= A <= 64, got ", A);
+  TORCH_CHECK(logits.size(2) >= 1 && logits.size(2) <= 1024,
+              "c51 loss supports 1 <= atoms <= 1024, got ", logits.size(2));
+  return logits.scalar_type() == torch::kBFloat16 ? 1 : 0;
+}
+
+// A vector of B values on the GPU with a non-negative element stride.
+void check_c51_vector(const torch::Tensor& t, const char* name,
+                      torch::ScalarType ty, int64_t B) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.dim() == 1 &&
+                  t.size(0) == B && t.stride(0) >= 0,
+              name, " must be a GPU vector of ", B, " ", ty, " values");
+}
+
+const long* check_c51_actions(const torch::Tensor& a_tm1, int64_t B,
+                              int64_t A) {
+  if (a_tm1.numel() == 0) {
+    TORCH_CHECK(A == 1, "c51 loss: an empty a_tm1 needs A == 1, got ", A);
+    return nullptr;
+  }
+  check_c51_vector(a_tm1, "a_tm1", torch::kInt64, B);
+  return a_tm1.data_ptr<long>();
+}
+
+void check_c51_rows(const torch::Tensor& t, const char* name, int64_t rows,
+                    int64_t cols) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32,
+              name, " must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(t.numel() == rows * cols && t.size(0) == rows, name,
+              " must hold ", rows, " x ", cols, " values");
+}
+
+void c51_loss_fwd(torch::Tensor logits_tm1, torch::Tensor atoms_tm1,
+                  torch::Tensor a_tm1, torch::Tensor r_t, torch::Tensor d_t,
+                  torch::Tensor logits_t, torch::Tensor atoms_t,
+                  torch::Tensor selector, torch::Tensor ce, torch::Tensor lse,
+                  torch::Tensor target) {
+  TORCH_CHECK(logits_tm1.dim() == 3, "logits_tm1 must be [B, A, M]");
+  const int64_t B = logits_tm1.size(0), A = logits_tm1.size(1);
+  const int tm1_bf16 = check_c51_logits(logits_tm1, "logits_tm1", B, A);
+  const int t_bf16 = check_c51_logits(logits_t, "logits_t", B, A);
+  const int64_t M = logits_tm1.size(2), N = logits_t.size(2);
+  const long* ap = check_c51_actions(a_tm1, B, A);
+  check_c51_rows(atoms_tm1, "atoms_tm1", M, 1);
+  check_c51_rows(atoms_t, "atoms_t", N, 1);
+  check_c51_vector(r_t, "r_t", torch::kFloat32, B);
+  check_c51_vector(d_t, "d_t", torch::kFloat32, B);
+  check_c51_rows(ce, "ce", B, 1);
+  check_c51_rows(lse, "lse", B, 1);
+  check_c51_rows(target, "target", B, M);
+  const float* sel = nullptr;
+  if (selector.numel() > 0) {
+    check_c51_rows(selector, "selector", B, A);
+    sel = selector.data_ptr<float>();
+  } else {
+    TORCH_CHECK(A == 1, "c51 loss: an empty selector needs A == 1, got ", A);
+  }
+  launch_c51_loss_fwd(logits_tm1.data_ptr(), atoms_tm1.data_ptr<float>(), ap,
+                      r_t.data_ptr<float>(), d_t.data_ptr<float>(),
+                      logits_t.data_ptr(), atoms_t.data_ptr<float>(), sel,
+                      ce.data_ptr<float>(), lse.data_ptr<float>(),
+                      target.data_ptr<float>(), (int)B, (int)A, (int)N,
+                      (int)M, tm1_bf16, t_bf16, ap ? (long)a_tm1.stride(0) : 0,
+                      (long)r_t.stride(0), (long)d_t.stride(0), cur_stream());
+}
+
+void c51_loss_bwd(torch::Tensor grad_ce, torch::Tensor logits_tm1,
+                  torch::Tensor a_tm1, torch::Tensor lse, torch::Tensor target,
+                  torch::Tensor dlogits) {
+  TORCH_CHECK(logits_tm1.dim() == 3, "logits_tm1 must be [B, A, M]");
+  const int64_t B = logits_tm1.size(0), A = logits_tm1.size(1);
+  const int is_bf16 = check_c51_logits(logits_tm1, "logits_tm1", B, A);
+  const int64_t M = logits_tm1.size(2);
+  check_c51_logits(dlogits, "dlogits", B, A);
+  TORCH_CHECK(dlogits.scalar_type() == logits_tm1.scalar_type() &&
+                  dlogits.size(2) == M,
+              "dlogits must match logits_tm1 in dtype and shape");
+  const long* ap = check_c51_actions(a_tm1, B, A);
+  check_c51_rows(lse, "lse", B, 1);
+  check_c51_rows(target, "target", B, M);
+  check_c51_vector(grad_ce, "grad_ce", torch::kFloat32, B);
+  launch_c51_loss_bwd(grad_ce.data_ptr<float>(), (long)grad_ce.stride(0),
+                      logits_tm1.data_ptr(), ap, lse.data_ptr<float>(),
+                      target.data_ptr<float>(), dlogits.data_ptr(), (int)B,
+                      (int)A, (int)M, is_bf16, ap ? (long)a_tm1.stride(0) : 0,
+                      cur_stream());
+}
+
 }  // namespace
 
 void sumtree_update(torch::Tensor tree, torch::Tensor idx,
@@ -751,6 +861,10 @@ void snake_step(torch::Tensor grid, torch::Tensor head_r,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("c51_loss_fwd", &c51_loss_fwd,
+        "C51 categorical TD loss: softmax + fixed-order projection + CE");
+  m.def("c51_loss_bwd", &c51_loss_bwd,
+        "C51 categorical TD loss: analytic logits backward");
   m.def("snake_step", &snake_step,
         "fused Snake env step (dynamics + metrics + autoreset + render)");
   m.def("rnn_scan", &rnn_scan,

@@ -6,7 +6,9 @@ target-actor action (:183-222), actor loss -E[Q] (:224-243).
 Simplification vs the reference: the reference samples n-step windows from a
 trajectory buffer (:477) and builds n-step rewards; here 1-step targets from
 the item buffer (the categorical-projection machinery is identical; n-step
-windows arrive with the trajectory-buffer integration of rainbow)."""
+windows arrive with the trajectory-buffer integration of rainbow).
+On the GPU the categorical TD loss runs in the fused c51.hip kernels
+(ops/losses.py)."""
 from __future__ import annotations
 
 import sys

@@ -1,5 +1,6 @@
 """Anakin C51 (parity: /root/reference/stoix/systems/q_learning/ff_c51.py):
-DistributionalDiscreteQNetwork head + categorical double-Q projection loss."""
+DistributionalDiscreteQNetwork head + categorical double-Q projection loss.
+On the GPU that loss runs in the fused c51.hip kernels (ops/losses.py)."""
 from __future__ import annotations
 
 import sys

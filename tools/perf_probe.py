@@ -3,6 +3,7 @@
 Run on a GPU box:  python tools/perf_probe.py
 Prints: fused-engine attach status, rollout vs epoch wall times (graphed and
 eager), and microbenchmarks of the individual fused kernels.
+`python tools/perf_probe.py c51` runs only the C51 loss microbenchmark.
 """
 from __future__ import annotations
 
@@ -24,6 +25,56 @@ def timeit(fn, iters=20, warmup=3):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters * 1e3  # ms
+
+
+def c51_loss_probe():
+    """C51 loss forward + backward at the Rainbow bench point (Snake: A = 4,
+    51 atoms, bf16 logits), fused kernels vs the torch chain
+    (STOIX_FUSED_C51=0) in the same process; eager, and replayed from a hip
+    graph as the Rainbow update runs it (no launch overhead)."""
+    from stoix_amd.ops import losses
+
+    dev = torch.device("cuda:0")
+    A, N = 4, 51
+    atoms = torch.linspace(-10.0, 10.0, N, device=dev)
+    for B in (4096, 1024):
+        g = torch.Generator(device=dev).manual_seed(B)
+        lt1 = (3 * torch.randn(B, A, N, device=dev, generator=g)).bfloat16().requires_grad_(True)
+        lt = (3 * torch.randn(B, A, N, device=dev, generator=g)).bfloat16()
+        sel = torch.randn(B, A, device=dev, generator=g)
+        a = torch.randint(0, A, (B,), device=dev, generator=g)
+        r = torch.randn(B, device=dev, generator=g)
+        d = 0.99 * (torch.rand(B, device=dev, generator=g) < 0.9).float()
+        w = torch.rand(B, device=dev, generator=g)
+
+        def fused():
+            ce = losses.c51_td_cross_entropy(lt1, atoms, a, r, d, lt, atoms, sel)
+            return torch.autograd.grad((w * ce).mean(), lt1)[0]
+
+        def chain():  # the Rainbow update's torch lines
+            with torch.no_grad():
+                best_a = sel.argmax(dim=-1)
+                probs_t = torch.softmax(lt.float(), dim=-1)
+                p_best = probs_t.gather(1, best_a.view(-1, 1, 1).expand(-1, 1, N)).squeeze(1)
+                target_z = r.unsqueeze(-1) + d.unsqueeze(-1) * atoms
+                target = losses.categorical_l2_project(target_z, p_best, atoms)
+            logits_a = lt1.float().gather(1, a.view(-1, 1, 1).expand(-1, 1, N)).squeeze(1)
+            ce = -(target * torch.log_softmax(logits_a, dim=-1)).sum(-1)
+            return torch.autograd.grad((w * ce).mean(), lt1)[0]
+
+        for name, fn in (("fused", fused), ("torch", chain)):
+            eager = timeit(fn, 200, 10) * 1e3
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                fn()
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                fn()
+            graphed = timeit(graph.replay, 200, 10) * 1e3
+            print(f"c51 loss fwd+bwd B={B:5d} {name}: eager {eager:8.1f} us"
+                  f"  graphed {graphed:8.1f} us")
 
 
 def main():
@@ -211,4 +262,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "c51" not in sys.argv[1:]:
+        main()
+    c51_loss_probe()
