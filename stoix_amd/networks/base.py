@@ -136,6 +136,24 @@ class ScannedRNN(nn.Module):
                      Hout, hT, empty, 0)
         return Hout, [hT]
 
+    def _hip_scan_train(self, x: Tensor, resets: Tensor, state: list, cell, kind):
+        """K13 training path: the same hoisted input projection, then the
+        scan as one autograd node (ops/rnn.py _RnnScan) whose forward is
+        bit-equal to ``_hip_scan`` and whose backward through time is one
+        HIP kernel; autograd carries dXp through the input linear."""
+        from stoix_amd.ops.rnn import rnn_scan
+
+        T, B = x.shape[:2]
+        xp = torch.nn.functional.linear(
+            x.reshape(T * B, -1), cell.weight_ih, cell.bias_ih
+        ).reshape(T, B, -1)
+        if kind == "lstm":
+            h0, c0 = state[0]
+            Hout, hT, cT = rnn_scan(xp, cell.weight_hh, cell.bias_hh, resets, h0, c0, kind)
+            return Hout, [(hT, cT)]
+        Hout, hT = rnn_scan(xp, cell.weight_hh, cell.bias_hh, resets, state[0], None, kind)
+        return Hout, [hT]
+
     def _hoisted_scan(self, x: Tensor, resets: Tensor, state: list, cell, kind):
         """Autograd training path with the input projection for ALL T
         hoisted into one GEMM (the cuDNN trick); only the [B,H]x[H,G*H]
@@ -177,15 +195,18 @@ class ScannedRNN(nn.Module):
         cell, kind = self._single_cell()
         if cell is not None:
             if (
-                not torch.is_grad_enabled()
-                and x.is_cuda
+                x.is_cuda
                 and self.hidden_dim in (128, 256)
                 and x.dtype == torch.float32
             ):
                 from stoix_amd import ops
+                from stoix_amd.ops.rnn import rnn_fused_enabled
 
-                if ops.have_ext():
-                    return self._hip_scan(x, resets, state, cell, kind)
+                if not torch.is_grad_enabled():
+                    if ops.have_ext():
+                        return self._hip_scan(x, resets, state, cell, kind)
+                elif rnn_fused_enabled() and ops.have_ext():
+                    return self._hip_scan_train(x, resets, state, cell, kind)
             return self._hoisted_scan(x, resets, state, cell, kind)
         T = x.shape[0]
         outs = []

@@ -111,6 +111,15 @@ void launch_ppo_gather_disc(const long*, int, const float*, int, int,
 void launch_rnn_scan(const float*, const void*, const float*,
                      const unsigned char*, const float*, const float*,
                      float*, float*, float*, int, int, int, int, void*);
+void launch_rnn_scan_train_fwd(const float*, const void*, const float*,
+                               const unsigned char*, const float*,
+                               const float*, float*, float*, float*, float*,
+                               float*, int, int, int, int, void*);
+void launch_rnn_scan_bwd(const float*, const float*, const float*,
+                         const float*, const float*, const float*,
+                         const float*, const float*, const unsigned char*,
+                         const void*, float*, float*, float*, float*, int,
+                         int, int, int, void*);
 void launch_snake_step(int*, long*, long*, long*, long*, int*, const long*,
                        int*, float*, int*, float*, int*, float*, float*,
                        float*, float*, unsigned char*, unsigned char*, int,
@@ -825,6 +834,94 @@ void rnn_scan(torch::Tensor Xp, torch::Tensor Whh, torch::Tensor bhh,
       cur_stream());
 }
 
+// Shape/dtype/contiguity check for the training scan's tensors (rnn.hip).
+void check_rnn_tensor(const torch::Tensor& t, const char* name,
+                      c10::ScalarType ty, at::IntArrayRef shape) {
+  TORCH_CHECK(t.is_cuda(), "rnn scan: ", name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == ty, "rnn scan: ", name, " has wrong dtype");
+  TORCH_CHECK(t.is_contiguous(), "rnn scan: ", name, " must be contiguous");
+  TORCH_CHECK(t.sizes() == shape, "rnn scan: ", name, " has shape ",
+              t.sizes(), ", expected ", shape);
+}
+
+// An optional [B, H] tensor: numel 0 stands for "absent" (null pointer).
+float* rnn_opt_state(const torch::Tensor& t, const char* name, int64_t B,
+                     int64_t H) {
+  if (t.numel() == 0) return nullptr;
+  check_rnn_tensor(t, name, torch::kFloat32, {B, H});
+  return t.data_ptr<float>();
+}
+
+void rnn_scan_train_fwd(torch::Tensor Xp, torch::Tensor Whh,
+                        torch::Tensor bhh, torch::Tensor resets,
+                        torch::Tensor h0, torch::Tensor c0,
+                        torch::Tensor Hout, torch::Tensor hT,
+                        torch::Tensor cT, torch::Tensor gates,
+                        torch::Tensor aux, int64_t lstm) {
+  TORCH_CHECK(Xp.dim() == 3 && h0.dim() == 2,
+              "rnn_scan_train_fwd: Xp is [T, B, G*H], h0 is [B, H]");
+  const int64_t T = Xp.size(0), B = Xp.size(1), H = h0.size(1);
+  const int64_t G = lstm ? 4 : 3;
+  TORCH_CHECK(H == 128 || H == 256, "rnn_scan_train_fwd supports H 128/256");
+  TORCH_CHECK(Xp.size(2) == G * H, "Xp gate dim mismatch");
+  TORCH_CHECK(T >= 1 && B >= 1, "rnn_scan_train_fwd needs T >= 1, B >= 1");
+  check_rnn_tensor(Xp, "Xp", torch::kFloat32, {T, B, G * H});
+  check_rnn_tensor(Whh, "Whh", torch::kBFloat16, {G * H, H});
+  check_rnn_tensor(bhh, "bhh", torch::kFloat32, {G * H});
+  check_rnn_tensor(resets, "resets", torch::kUInt8, {T, B});
+  check_rnn_tensor(h0, "h0", torch::kFloat32, {B, H});
+  check_rnn_tensor(Hout, "Hout", torch::kFloat32, {T, B, H});
+  check_rnn_tensor(hT, "hT", torch::kFloat32, {B, H});
+  check_rnn_tensor(gates, "gates", torch::kFloat32, {T, B, G * H});
+  check_rnn_tensor(aux, "aux", torch::kFloat32, {T, B, H});
+  const float* c0p = lstm ? rnn_opt_state(c0, "c0", B, H) : nullptr;
+  float* cTp = lstm ? rnn_opt_state(cT, "cT", B, H) : nullptr;
+  launch_rnn_scan_train_fwd(
+      Xp.data_ptr<float>(), Whh.data_ptr(), bhh.data_ptr<float>(),
+      resets.data_ptr<unsigned char>(), h0.data_ptr<float>(), c0p,
+      Hout.data_ptr<float>(), hT.data_ptr<float>(), cTp,
+      gates.data_ptr<float>(), aux.data_ptr<float>(), (int)T, (int)B, (int)H,
+      (int)lstm, cur_stream());
+}
+
+void rnn_scan_bwd(torch::Tensor dHout, torch::Tensor dhT, torch::Tensor dcT,
+                  torch::Tensor gates, torch::Tensor aux, torch::Tensor Hout,
+                  torch::Tensor h0, torch::Tensor c0, torch::Tensor resets,
+                  torch::Tensor WhhT, torch::Tensor dXp, torch::Tensor dHg,
+                  torch::Tensor dh0, torch::Tensor dc0, int64_t lstm) {
+  TORCH_CHECK(gates.dim() == 3 && h0.dim() == 2,
+              "rnn_scan_bwd: gates is [T, B, G*H], h0 is [B, H]");
+  const int64_t T = gates.size(0), B = gates.size(1), H = h0.size(1);
+  const int64_t G = lstm ? 4 : 3;
+  TORCH_CHECK(H == 128 || H == 256, "rnn_scan_bwd supports H 128/256");
+  TORCH_CHECK(gates.size(2) == G * H, "gates gate dim mismatch");
+  TORCH_CHECK(T >= 1 && B >= 1, "rnn_scan_bwd needs T >= 1, B >= 1");
+  check_rnn_tensor(dHout, "dHout", torch::kFloat32, {T, B, H});
+  check_rnn_tensor(gates, "gates", torch::kFloat32, {T, B, G * H});
+  check_rnn_tensor(aux, "aux", torch::kFloat32, {T, B, H});
+  check_rnn_tensor(Hout, "Hout", torch::kFloat32, {T, B, H});
+  check_rnn_tensor(h0, "h0", torch::kFloat32, {B, H});
+  check_rnn_tensor(resets, "resets", torch::kUInt8, {T, B});
+  check_rnn_tensor(WhhT, "WhhT", torch::kBFloat16, {H, G * H});
+  check_rnn_tensor(dXp, "dXp", torch::kFloat32, {T, B, G * H});
+  check_rnn_tensor(dh0, "dh0", torch::kFloat32, {B, H});
+  // GRU: dHg differs from dXp in the n block; LSTM: dXp is dHg.
+  float* dHgp = nullptr;
+  if (!lstm) {
+    check_rnn_tensor(dHg, "dHg", torch::kFloat32, {T, B, G * H});
+    dHgp = dHg.data_ptr<float>();
+  }
+  launch_rnn_scan_bwd(
+      dHout.data_ptr<float>(), rnn_opt_state(dhT, "dhT", B, H),
+      lstm ? rnn_opt_state(dcT, "dcT", B, H) : nullptr,
+      gates.data_ptr<float>(), aux.data_ptr<float>(), Hout.data_ptr<float>(),
+      h0.data_ptr<float>(), lstm ? rnn_opt_state(c0, "c0", B, H) : nullptr,
+      resets.data_ptr<unsigned char>(), WhhT.data_ptr(),
+      dXp.data_ptr<float>(), dHgp, dh0.data_ptr<float>(),
+      lstm ? rnn_opt_state(dc0, "dc0", B, H) : nullptr, (int)T, (int)B,
+      (int)H, (int)lstm, cur_stream());
+}
+
 void snake_step(torch::Tensor grid, torch::Tensor head_r,
                 torch::Tensor head_c, torch::Tensor fruit_r,
                 torch::Tensor fruit_c, torch::Tensor length,
@@ -869,6 +966,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused Snake env step (dynamics + metrics + autoreset + render)");
   m.def("rnn_scan", &rnn_scan,
         "fused done-masked GRU/LSTM sequence scan (K13)");
+  m.def("rnn_scan_train_fwd", &rnn_scan_train_fwd,
+        "K13 training forward: rnn_scan + saved gates/aux for the backward");
+  m.def("rnn_scan_bwd", &rnn_scan_bwd,
+        "K13 backward through time: dXp, dHg, dh0/dc0 from dHout");
   m.def("policy_value_step_disc", &policy_value_step_disc,
         "fused actor+critic fwd, categorical Gumbel-max sample (MFMA)");
   m.def("ppo_head_loss_disc", &ppo_head_loss_disc,
