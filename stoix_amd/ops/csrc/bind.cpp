@@ -87,6 +87,12 @@ void launch_wgrad(const void*, const void*, float*, long, long, long, int,
 void launch_slab_reduce(float*, void*, long, long, float*, long*, void*);
 void launch_bump_add(unsigned int*, unsigned int, void*);
 void launch_tr16_probe(const void*, float*, int, void*);
+int launch_wgrad_pair(const void*, const void*, float*, long, long, long, int,
+                      const void*, const void*, float*, long, long, long, int,
+                      int, int, int, int, void*);
+void launch_slab_reduce_pair(const float*, void*, long, long, float*, long*,
+                             const float*, void*, long, long, float*, long*,
+                             void*);
 void launch_sumtree_update(float*, const long*, const float*, long, int, int,
                            void*);
 void launch_sumtree_sample(const float*, const float*, long*, long, int, int,
@@ -677,6 +683,82 @@ void slab_reduce(torch::Tensor slab, torch::Tensor grad16,
                      slab.size(1), grad16.numel(), sq, st, cur_stream());
 }
 
+// Both nets' dW = dZ^T @ X and db = colsum(dZ) in one launch of the
+// pipelined kernel (wgrad.hip); bit-equal to two wgrad() calls. Returns true
+// if the paired kernel covered the shape, false if the launcher fell back to
+// the old kernels.
+static void wgrad_pair_slab_check(const torch::Tensor& slab, int64_t dW_off,
+                                  int64_t db_off, int64_t nv, int64_t K) {
+  TORCH_CHECK(slab.dim() == 2 && slab.size(0) >= 64,
+              "wgrad_pair: slab must be [>=64, stride]");
+  TORCH_CHECK(nv >= 1, "wgrad_pair: n_valid must be >= 1");
+  TORCH_CHECK(dW_off >= 0 && dW_off + nv * K <= slab.size(1),
+              "wgrad_pair: dW range outside the slab");
+  TORCH_CHECK(db_off < 0 || db_off + nv <= slab.size(1),
+              "wgrad_pair: db range outside the slab");
+}
+
+bool wgrad_pair(torch::Tensor dZ0, torch::Tensor X0, torch::Tensor slab0,
+                int64_t dW_off0, int64_t db_off0, int64_t n_valid0,
+                torch::Tensor dZ1, torch::Tensor X1, torch::Tensor slab1,
+                int64_t dW_off1, int64_t db_off1, int64_t n_valid1,
+                int64_t variant = -1) {
+  CHK(dZ0, torch::kBFloat16);
+  CHK(X0, torch::kBFloat16);
+  CHK(slab0, torch::kFloat32);
+  CHK(dZ1, torch::kBFloat16);
+  CHK(X1, torch::kBFloat16);
+  CHK(slab1, torch::kFloat32);
+  TORCH_CHECK(dZ0.dim() == 2 && X0.dim() == 2 && dZ1.dim() == 2 &&
+                  X1.dim() == 2, "wgrad_pair: operands must be 2-D");
+  int64_t S = dZ0.size(0), N_STRIDE = dZ0.size(1), K = X0.size(1);
+  TORCH_CHECK(X0.size(0) == S && dZ1.size(0) == S && X1.size(0) == S,
+              "wgrad_pair: dZ/X row mismatch");
+  TORCH_CHECK(dZ1.size(1) == N_STRIDE && X1.size(1) == K,
+              "wgrad_pair: the two nets' operand widths differ");
+  TORCH_CHECK(S % (4 * 32) == 0, "wgrad_pair: S must be a multiple of 128");
+  TORCH_CHECK(K % 32 == 0, "wgrad_pair: K must be a multiple of 32");
+  TORCH_CHECK(N_STRIDE % 16 == 0, "wgrad_pair: dZ width must be a multiple of 16");
+  TORCH_CHECK(n_valid0 <= N_STRIDE && n_valid1 <= N_STRIDE,
+              "wgrad_pair: n_valid exceeds the dZ width");
+  wgrad_pair_slab_check(slab0, dW_off0, db_off0, n_valid0, K);
+  wgrad_pair_slab_check(slab1, dW_off1, db_off1, n_valid1, K);
+  return launch_wgrad_pair(
+             dZ0.data_ptr(), X0.data_ptr(), slab0.data_ptr<float>(),
+             (long)dW_off0, (long)db_off0, (long)slab0.size(1), (int)n_valid0,
+             dZ1.data_ptr(), X1.data_ptr(), slab1.data_ptr<float>(),
+             (long)dW_off1, (long)db_off1, (long)slab1.size(1), (int)n_valid1,
+             (int)S, (int)N_STRIDE, (int)K, (int)variant, cur_stream()) != 0;
+}
+
+// One launch over both chains' slabs; same sums and Adam prologue as
+// slab_reduce(), but the slabs are left as they are (not zeroed).
+void slab_reduce_pair(torch::Tensor slab0, torch::Tensor grad0,
+                      torch::Tensor sqnorm0, torch::Tensor step0,
+                      torch::Tensor slab1, torch::Tensor grad1,
+                      torch::Tensor sqnorm1, torch::Tensor step1) {
+  CHK(slab0, torch::kFloat32);
+  CHK(grad0, torch::kBFloat16);
+  CHK(slab1, torch::kFloat32);
+  CHK(grad1, torch::kBFloat16);
+  TORCH_CHECK(slab0.dim() == 2 && slab0.size(0) == 64 && slab1.dim() == 2 &&
+                  slab1.size(0) == 64, "slab_reduce_pair: slabs must be [64, n]");
+  TORCH_CHECK(grad0.numel() <= slab0.size(1) && grad1.numel() <= slab1.size(1),
+              "slab_reduce_pair: grad longer than a slab image");
+  TORCH_CHECK((sqnorm0.numel() > 0) == (step0.numel() > 0) &&
+                  (sqnorm1.numel() > 0) == (step1.numel() > 0),
+              "slab_reduce_pair: sqnorm and step_t go together");
+  float* sq0 = sqnorm0.numel() > 0 ? sqnorm0.data_ptr<float>() : nullptr;
+  long* st0 = step0.numel() > 0 ? step0.data_ptr<long>() : nullptr;
+  float* sq1 = sqnorm1.numel() > 0 ? sqnorm1.data_ptr<float>() : nullptr;
+  long* st1 = step1.numel() > 0 ? step1.data_ptr<long>() : nullptr;
+  launch_slab_reduce_pair(slab0.data_ptr<float>(), grad0.data_ptr(),
+                          slab0.size(1), grad0.numel(), sq0, st0,
+                          slab1.data_ptr<float>(), grad1.data_ptr(),
+                          slab1.size(1), grad1.numel(), sq1, st1,
+                          cur_stream());
+}
+
 void bump_add(torch::Tensor draw_buf, int64_t n) {
   launch_bump_add((unsigned int*)draw_buf.data_ptr<int>(), (unsigned int)n,
                   cur_stream());
@@ -1015,6 +1097,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ntb") = 0);
   m.def("slab_reduce", &slab_reduce,
         "sum wgrad slabs into flat bf16 grads (+ fused Adam prologue)");
+  m.def("wgrad_pair", &wgrad_pair,
+        "both nets' split-K wgrads in one pipelined launch -> slabs",
+        py::arg("dZ0"), py::arg("X0"), py::arg("slab0"), py::arg("dW_off0"),
+        py::arg("db_off0"), py::arg("n_valid0"), py::arg("dZ1"),
+        py::arg("X1"), py::arg("slab1"), py::arg("dW_off1"),
+        py::arg("db_off1"), py::arg("n_valid1"), py::arg("variant") = -1);
+  m.def("slab_reduce_pair", &slab_reduce_pair,
+        "both chains' slabs -> flat bf16 grads, slabs left un-zeroed");
   m.def("bump_add", &bump_add, "add N to a device RNG draw counter");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
 }

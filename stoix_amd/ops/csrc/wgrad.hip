@@ -14,6 +14,10 @@
 // 32-deep s-tiles of dZ and X into LDS *transposed* (scatter b16 writes,
 // contiguous ds_read_b128 fragment reads) and issues KPG
 // mfma_f32_16x16x32_bf16 per s-step.
+//
+// wgrad_pair_kernel / slab_reduce_pair_kernel (further down) are what the
+// PPO engine runs by default: the same sums, both nets per launch, tiles
+// staged row-major and read transposed, loads pipelined behind the MFMAs.
 #include "common.h"
 #include <cstdlib>
 #include <hip/hip_bf16.h>
@@ -179,6 +183,267 @@ extern "C" __global__ void slab_reduce_kernel(float* __restrict__ slab,
   }
 }
 
+// ------------------------------------------------- pipelined, paired wgrad
+// Same result as wgrad_kernel, bit for bit (same slices, one accumulator
+// chain per 16x16 tile, one MFMA per 32-row step in ascending row order,
+// row s0+8g+j in k-slot (g, j); same db sum), but:
+//  * both nets in one launch (blockIdx.z picks the net),
+//  * one workgroup = one slice x (WN*NTW*16) n x (WK*KTW*16) k, the four
+//    waves laid out WN x WK over the tile, all staging cooperative,
+//  * s-tiles are stored ROW-major in LDS with 16-byte writes and the MFMA
+//    operands come out of ds_read_b64_tr_b16 already transposed (two reads
+//    per fragment: block rows 8g..8g+3 and 8g+4..8g+7),
+//  * register prefetch + LDS double buffer: the global loads of stage i+1
+//    (SB 32-row steps) are in flight while stage i's MFMAs run; one barrier
+//    per stage.
+//
+// LDS image of a [R rows][C cols] tile: byte offset of (row, col) =
+// row*P + (row>>3)*128 + col*2 with P = the row bytes padded up to
+// 32 (mod 64). A 32-lane half of a transposed read takes rows r..r+3 and
+// r+8..r+11 of one 32-byte column group: with P = 32*odd the first four
+// rows land on four distinct 8-bank groups whose indices differ by
+// o, 2o, 3o (mod 8, o odd), never by 4, and the 128-byte step per 8 rows
+// moves the other four by 32 banks = 4 groups, so the eight 32-byte
+// segments tile the 64 banks: conflict-free by the (a/4)%64 bank rule.
+struct WgradNet {
+  const bf16_t* dZ;  // [S, N_STRIDE]
+  const bf16_t* X;   // [S, K]
+  float* slab;       // [WG_SLICES, slab_stride]
+  long dW_off, db_off, slab_stride;
+  int N_VALID;
+};
+
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+__host__ __device__ constexpr int wp_pitch(int row_bytes) {
+  return ((row_bytes + 31) / 64) * 64 + 32;
+}
+
+__device__ __forceinline__ bf16x8 wp_tr_frag(const unsigned char* p,
+                                             int pitch) {
+  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p);
+  bf16x4 hi =
+      __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + 4 * pitch));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <int NTW, int KTW, int WN, int WK, int SB>
+__launch_bounds__(256) __global__ void wgrad_pair_kernel(
+    WgradNet net0, WgradNet net1, int S, int N_STRIDE, int K, int n_slices,
+    int kblocks, int slice_major) {
+  static_assert(WN * WK == 4, "four waves");
+  constexpr int TN = WN * NTW * 16, TK = WK * KTW * 16;
+  constexpr int CZ = TN / 8, CX = TK / 8;  // 16-byte chunks per tile row
+  constexpr int PZ = wp_pitch(TN * 2), PX = wp_pitch(TK * 2);
+  constexpr int ROWS = 32 * SB;
+  constexpr int ZSTEP = 32 * PZ + 4 * 128, XSTEP = 32 * PX + 4 * 128;
+  constexpr int ZB = SB * ZSTEP, XB = SB * XSTEP;
+  constexpr int NZ = ROWS * CZ, NX = ROWS * CX;
+  constexpr int LZ = (NZ + 255) / 256, LX = (NX + 255) / 256;
+  static_assert(2 * (ZB + XB) <= 160 * 1024, "gfx950 LDS");
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * (ZB + XB)];
+
+  const bool second = blockIdx.z != 0;
+  const bf16_t* __restrict__ dZ = second ? net1.dZ : net0.dZ;
+  const bf16_t* __restrict__ X = second ? net1.X : net0.X;
+  float* __restrict__ slab = second ? net1.slab : net0.slab;
+  const long dW_off = second ? net1.dW_off : net0.dW_off;
+  const long db_off = second ? net1.db_off : net0.db_off;
+  const long slab_stride = second ? net1.slab_stride : net0.slab_stride;
+  const int N_VALID = second ? net1.N_VALID : net0.N_VALID;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  // wave id as a scalar, so the per-wave branches are scalar branches
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wn = wid / WK, wk = wid % WK;
+  // slice_major: the slice runs along blockIdx.x, so the workgroups that
+  // share one slice's dZ / X rows have linear ids a multiple of 8 apart and
+  // land on the same XCD (one L2)
+  const int tile = slice_major ? blockIdx.y : blockIdx.x;
+  const int n0 = (tile / kblocks) * TN;
+  const int kblk = tile % kblocks;
+  const int k0 = kblk * TK;
+  const int slice = slice_major ? blockIdx.x : blockIdx.y;  // [0, n_slices)
+  const int s_per = S / n_slices;
+  const int s_begin = slice * s_per;
+  const int s_end = s_begin + s_per;
+  const int steps = s_per / 32;
+  const int nstages = (steps + SB - 1) / SB;
+  const bool do_db = db_off >= 0 && kblk == 0;  // workgroup-uniform
+
+  f32x4 acc[NTW][KTW];
+#pragma unroll
+  for (int u = 0; u < NTW; ++u)
+#pragma unroll
+    for (int t = 0; t < KTW; ++t) acc[u][t] = {0.f, 0.f, 0.f, 0.f};
+  float db_acc[NTW];
+#pragma unroll
+  for (int u = 0; u < NTW; ++u) db_acc[u] = 0.0f;
+
+  // transposed-read lane address: lane 4q+p of 16-lane group g supplies
+  // row 8g+q, columns 4p..4p+3 of the block; it receives column (lane&15)
+  const int g = lane >> 4;
+  const int q = (lane >> 2) & 3, p = lane & 3;
+  const int zl = (8 * g + q) * PZ + g * 128 + (wn * NTW * 16 + 4 * p) * 2;
+  const int xl = (8 * g + q) * PX + g * 128 + (wk * KTW * 16 + 4 * p) * 2;
+
+  bf16x8 rz[LZ], rx[LX];  // register prefetch of one stage
+
+  auto gload = [&](int st) {
+    const int r0 = s_begin + st * ROWS;
+#pragma unroll
+    for (int i = 0; i < LZ; ++i) {
+      const int c = tid + i * 256;
+      if (NZ % 256 == 0 || c < NZ) {
+        // rows past the slice end (a partial last stage) are clamped to
+        // its last row: in bounds, staged, never consumed
+        int gr = r0 + c / CZ;
+        gr = gr < s_end ? gr : s_end - 1;
+        rz[i] = *reinterpret_cast<const bf16x8*>(
+            dZ + (long)gr * N_STRIDE + n0 + (c % CZ) * 8);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < LX; ++i) {
+      const int c = tid + i * 256;
+      if (NX % 256 == 0 || c < NX) {
+        int gr = r0 + c / CX;
+        gr = gr < s_end ? gr : s_end - 1;
+        rx[i] = *reinterpret_cast<const bf16x8*>(
+            X + (long)gr * K + k0 + (c % CX) * 8);
+      }
+    }
+  };
+  auto lwrite = [&](int buf) {
+    unsigned char* zb = lds + buf * (ZB + XB);
+    unsigned char* xb = zb + ZB;
+#pragma unroll
+    for (int i = 0; i < LZ; ++i) {
+      const int c = tid + i * 256;
+      if (NZ % 256 == 0 || c < NZ) {
+        const int row = c / CZ;
+        *reinterpret_cast<bf16x8*>(zb + row * PZ + (row >> 3) * 128 +
+                                   (c % CZ) * 16) = rz[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < LX; ++i) {
+      const int c = tid + i * 256;
+      if (NX % 256 == 0 || c < NX) {
+        const int row = c / CX;
+        *reinterpret_cast<bf16x8*>(xb + row * PX + (row >> 3) * 128 +
+                                   (c % CX) * 16) = rx[i];
+      }
+    }
+  };
+
+  gload(0);
+  lwrite(0);
+  __syncthreads();
+  for (int st = 0; st < nstages; ++st) {
+    const bool more = st + 1 < nstages;
+    if (more) gload(st + 1);
+    const unsigned char* zb = lds + (st & 1) * (ZB + XB);
+    const unsigned char* xb = zb + ZB;
+    const int nst = steps - st * SB;  // valid steps in this stage (>= 1)
+    // every branch below is workgroup- or wave-uniform: the transposed
+    // reads always run with EXEC all ones
+#pragma unroll
+    for (int sb = 0; sb < SB; ++sb) {
+      if (sb < nst) {
+        bf16x8 a[NTW];
+#pragma unroll
+        for (int u = 0; u < NTW; ++u)
+          a[u] = wp_tr_frag(zb + zl + sb * ZSTEP + u * 32, PZ);
+#pragma unroll
+        for (int t = 0; t < KTW; ++t) {
+          const bf16x8 b = wp_tr_frag(xb + xl + sb * XSTEP + t * 32, PX);
+#pragma unroll
+          for (int u = 0; u < NTW; ++u)
+            acc[u][t] = MFMA_BF16_16x16x32(a[u], b, acc[u][t], 0, 0, 0);
+        }
+        // bias partials; the WK waves that share an n-range split its tiles
+        if (do_db) {
+#pragma unroll
+          for (int u = 0; u < NTW; ++u) {
+            if (u % WK == wk) {
+#pragma unroll
+              for (int j = 0; j < 8; ++j) db_acc[u] += (float)a[u][j];
+            }
+          }
+        }
+      }
+    }
+    if (more) lwrite((st + 1) & 1);
+    __syncthreads();
+  }
+
+  // ---- write this workgroup's part of slab image `slice`
+  float* out = slab + (long)slice * slab_stride;
+  const int col = lane & 15;
+#pragma unroll
+  for (int u = 0; u < NTW; ++u) {
+    const int nb = n0 + (wn * NTW + u) * 16;
+#pragma unroll
+    for (int t = 0; t < KTW; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = nb + g * 4 + r;  // D row = n (A is dZ^T)
+        if (n < N_VALID)
+          out[dW_off + (long)n * K + k0 + (wk * KTW + t) * 16 + col] =
+              acc[u][t][r];
+      }
+    }
+    if (do_db && u % WK == wk) {
+      float d = db_acc[u];
+      d += __shfl_xor(d, 16);
+      d += __shfl_xor(d, 32);
+      if (g == 0 && nb + col < N_VALID) out[db_off + nb + col] = d;
+    }
+  }
+}
+
+// Both chains' slabs -> their flat bf16 grads in one launch (blockIdx.y
+// picks the chain), same ascending sum over the WG_SLICES images and same
+// fused Adam prologue as slab_reduce_kernel, but NO stores to the slab.
+// That is safe wherever the slab is only ever filled by the wgrad kernels
+// with a fixed set of (offset, shape) calls, as in the PPO engine: they
+// store (never accumulate), so every valid element of the used images is
+// overwritten by the next minibatch's wgrads before it is read again, and
+// unused images and padding rows are never written, so they keep the zeros
+// the slab was allocated with.
+extern "C" __launch_bounds__(256) __global__ void slab_reduce_pair_kernel(
+    const float* __restrict__ slab0, __bf16* __restrict__ grad0, long stride0,
+    long n0, float* __restrict__ sqnorm0, long* __restrict__ step0,
+    const float* __restrict__ slab1, __bf16* __restrict__ grad1, long stride1,
+    long n1, float* __restrict__ sqnorm1, long* __restrict__ step1) {
+  const bool second = blockIdx.y != 0;
+  const float* __restrict__ slab = second ? slab1 : slab0;
+  __bf16* __restrict__ grad16 = second ? grad1 : grad0;
+  const long slab_stride = second ? stride1 : stride0;
+  const long n = second ? n1 : n0;
+  float* sqnorm = second ? sqnorm1 : sqnorm0;
+  long* step_t = second ? step1 : step0;
+  if (sqnorm && blockIdx.x == 0 && threadIdx.x == 0) {
+    *sqnorm = 0.0f;
+    *step_t += 1;
+  }
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    // all 64 loads go out before the first add (the compiler left two in
+    // flight when load and add shared one loop); the adds keep their order
+    float v[WG_SLICES];
+#pragma unroll
+    for (int z = 0; z < WG_SLICES; ++z) v[z] = slab[(long)z * slab_stride + i];
+    float s = 0.0f;
+#pragma unroll
+    for (int z = 0; z < WG_SLICES; ++z) s += v[z];
+    grad16[i] = (__bf16)s;
+  }
+}
+
 // ------------------------------------------------------------- tr probe
 // Empirically maps __builtin_amdgcn_ds_read_tr16_b64_v4bf16: stages 1024
 // known bf16 values linearly in LDS, issues the tr read with per-lane base
@@ -264,6 +529,97 @@ extern "C" void launch_slab_reduce(float* slab, void* grad16,
   hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(threads), 0,
                      (hipStream_t)stream, slab, (__bf16*)grad16, slab_stride,
                      n, sqnorm, step_t);
+}
+
+// Paired launch. Tiles per shape (tools/wgrad_sweep.py --pair):
+//   heads  N_STRIDE=16, K in {128,256,512}: 16n x 128k, 2 steps a stage
+//   K in {32,64,96}  (layer 1):             128n x K, waves split n
+//   K = 128:                                128n x 128k, waves split k
+//   K in {256,512}   (layer 2):             128n x 128k, waves split k,
+//                                           slice-major grid
+// variant >= 0 picks one of the alternatives the sweep compares. A shape
+// outside this table goes to the old kernels, one launch per net, never to
+// a neighbouring instantiation. Returns 1 if the paired kernel ran.
+extern "C" int launch_wgrad_pair(
+    const void* dZ0, const void* X0, float* slab0, long dW_off0, long db_off0,
+    long stride0, int nv0, const void* dZ1, const void* X1, float* slab1,
+    long dW_off1, long db_off1, long stride1, int nv1, int S, int N_STRIDE,
+    int K, int variant, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int n_slices = WG_SLICES;
+  if (const char* e = getenv("STOIX_WGRAD_SLICES")) {
+    int v = atoi(e);
+    if (v >= 4 && v <= WG_SLICES) n_slices = v;
+  }
+  while (n_slices > 4 && (S % (n_slices * 32)) != 0) n_slices >>= 1;
+  // variant < 0: the baked winners = variant 0, except layer 2 (K 256/512)
+  // = variant 6. variants >= 4: the tiles of variant - 4 with the slice
+  // along blockIdx.x (needs n_slices % 8 == 0 to line up with the 8 XCDs)
+  if (variant < 0) variant = (K == 256 || K == 512) && N_STRIDE != 16 ? 6 : 0;
+  const int slice_major = variant >= 4 && n_slices % 8 == 0;
+  if (variant >= 4) variant -= 4;
+  WgradNet a{(const bf16_t*)dZ0, (const bf16_t*)X0, slab0, dW_off0, db_off0,
+             stride0, nv0};
+  WgradNet b{(const bf16_t*)dZ1, (const bf16_t*)X1, slab1, dW_off1, db_off1,
+             stride1, nv1};
+#define WPAIR_LAUNCH(NTW, KTW, WN, WK, SB)                                   \
+  do {                                                                       \
+    constexpr int TN = WN * NTW * 16, TK = WK * KTW * 16;                    \
+    int kblocks = K / TK;                                                    \
+    int tiles = (N_STRIDE / TN) * kblocks;                                   \
+    dim3 grid(slice_major ? n_slices : tiles, slice_major ? tiles : n_slices, \
+              2), block(256);                                                \
+    hipLaunchKernelGGL((wgrad_pair_kernel<NTW, KTW, WN, WK, SB>), grid,      \
+                       block, 0, s, a, b, S, N_STRIDE, K, n_slices,          \
+                       kblocks, slice_major);                                \
+    return 1;                                                                \
+  } while (0)
+  const bool ok = (S % (n_slices * 32)) == 0 && n_slices % 4 == 0;
+  const bool hid = N_STRIDE == 128 || N_STRIDE == 256 || N_STRIDE == 512;
+  if (ok && N_STRIDE == 16 && nv0 >= 1 && nv0 <= 16 && nv1 >= 1 &&
+      nv1 <= 16 && (K == 128 || K == 256 || K == 512)) {
+    if (variant == 1) WPAIR_LAUNCH(1, 2, 1, 4, 1);
+    if (variant == 2) WPAIR_LAUNCH(1, 1, 1, 4, 2);  // 16n x 64k
+    if (variant == 3) WPAIR_LAUNCH(1, 2, 1, 4, 4);
+    WPAIR_LAUNCH(1, 2, 1, 4, 2);
+  }
+  if (ok && hid && nv0 == N_STRIDE && nv1 == N_STRIDE) {
+    if (K == 32) {
+      if (variant == 1) WPAIR_LAUNCH(2, 2, 4, 1, 1);
+      if (variant == 2) WPAIR_LAUNCH(1, 2, 4, 1, 2);  // 64n x 32k
+      if (variant == 3) WPAIR_LAUNCH(2, 2, 4, 1, 4);
+      WPAIR_LAUNCH(2, 2, 4, 1, 2);
+    }
+    if (K == 64) WPAIR_LAUNCH(2, 4, 4, 1, 2);
+    if (K == 96) WPAIR_LAUNCH(2, 6, 4, 1, 1);
+    if (K == 128) WPAIR_LAUNCH(8, 2, 1, 4, 1);
+    if (K == 256 || K == 512) {
+      if (variant == 1) WPAIR_LAUNCH(4, 4, 1, 4, 1);  // 64n x 256k
+      if (variant == 2) WPAIR_LAUNCH(8, 2, 1, 4, 1);  // 128n x 128k
+      if (variant == 3) WPAIR_LAUNCH(8, 4, 1, 4, 2);
+      WPAIR_LAUNCH(8, 4, 1, 4, 1);
+    }
+  }
+#undef WPAIR_LAUNCH
+  launch_wgrad(dZ0, X0, slab0, dW_off0, db_off0, stride0, S, N_STRIDE, K, nv0,
+               0, 0, stream);
+  launch_wgrad(dZ1, X1, slab1, dW_off1, db_off1, stride1, S, N_STRIDE, K, nv1,
+               0, 0, stream);
+  return 0;
+}
+
+extern "C" void launch_slab_reduce_pair(
+    const float* slab0, void* grad0, long stride0, long n0, float* sqnorm0,
+    long* step0, const float* slab1, void* grad1, long stride1, long n1,
+    float* sqnorm1, long* step1, void* stream) {
+  int threads = 256;
+  long nmax = n0 > n1 ? n0 : n1;
+  long want = (nmax + threads - 1) / threads;
+  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
+  hipLaunchKernelGGL(slab_reduce_pair_kernel, dim3(blocks, 2), dim3(threads),
+                     0, (hipStream_t)stream, slab0, (__bf16*)grad0, stride0,
+                     n0, sqnorm0, step0, slab1, (__bf16*)grad1, stride1, n1,
+                     sqnorm1, step1);
 }
 
 extern "C" void launch_tr16_probe(const void* in, float* out, int base_mode,

@@ -22,7 +22,8 @@ stoix_amd/ops/csrc/mlp.hip:
                  (head dgrads formed inside the layer-2 silu backward),
                  one silu_bwd for layer 1, dH1 as one batched bmm against the
                  adjacent-W2 [2, H, H] view, split-K wgrads into per-chain
-                 slabs -> slab_reduce per chain
+                 slabs (wgrad_pair: both nets per launch) -> one
+                 slab_reduce_pair over both chains
                  -> ONE bf16 RCCL all-reduce over both chains' shared
                  grad buffer
                  -> fused_adam_bf16 per chain (clip + Adam + bf16 mirror;
@@ -367,6 +368,11 @@ class FusedPPOEngine:
         _heads = _os.environ.get("STOIX_FUSED_HEADS", "1")
         self.fused_heads = _heads != "0"
         self.fused_vpred = _heads == "2"
+        # STOIX_FUSED_WGRAD: 1 (default) = the pipelined wgrad kernel, both
+        # nets per launch (3 launches) + one paired slab reduce that leaves
+        # the slabs un-zeroed; 0 = six wgrad launches + two zeroing reduces.
+        # Same gradients bit for bit (wgrad.hip keeps the summation order).
+        self.fused_wgrad = _os.environ.get("STOIX_FUSED_WGRAD", "1") != "0"
         self.no_vpred = z(0)
         # side-stream gather prefetch. Measured SLOWER (28.0 vs 26.8
         # ms/step): the backward kernels already fill all 256 CUs, so the
@@ -683,23 +689,36 @@ class FusedPPOEngine:
             # stacked [2, S, H] buffers and the two dH1 GEMMs go as one
             # bmm against the adjacent-W2 view.
             ao, co = ac.offsets, cc.offsets
-            ext.wgrad(self.dhead, self.H2[0], ac.slab, ao["Wh"], ao["bh"], 16)
-            ext.wgrad(self.dv16, self.H2[1], cc.slab, co["Wv"], co["bv"], 1)
+            pair = self.fused_wgrad
+            if pair:
+                ext.wgrad_pair(self.dhead, self.H2[0], ac.slab, ao["Wh"], ao["bh"], 16,
+                               self.dv16, self.H2[1], cc.slab, co["Wv"], co["bv"], 1)
+            else:
+                ext.wgrad(self.dhead, self.H2[0], ac.slab, ao["Wh"], ao["bh"], 16)
+                ext.wgrad(self.dv16, self.H2[1], cc.slab, co["Wv"], co["bv"], 1)
             if self.fused_heads:
                 ext.heads_bwd_silu(self.dhead, self.dv, a16["Wh"], c16["Wv"],
                                    self.Z2, self.dZ2)
             else:
                 ext.silu_bwd(self.dH2, self.Z2, self.dZ2)
-            ext.wgrad(self.dZ2[0], self.H1[0], ac.slab, ao["W2"], ao["b2"], self.H)
-            ext.wgrad(self.dZ2[1], self.H1[1], cc.slab, co["W2"], co["b2"], self.H)
+            if pair:
+                ext.wgrad_pair(self.dZ2[0], self.H1[0], ac.slab, ao["W2"], ao["b2"], self.H,
+                               self.dZ2[1], self.H1[1], cc.slab, co["W2"], co["b2"], self.H)
+            else:
+                ext.wgrad(self.dZ2[0], self.H1[0], ac.slab, ao["W2"], ao["b2"], self.H)
+                ext.wgrad(self.dZ2[1], self.H1[1], cc.slab, co["W2"], co["b2"], self.H)
             if self.use_bmm:
                 torch.bmm(self.dZ2, self.W2pair, out=self.dH1)
             else:
                 torch.mm(self.dZ2[0], a16["W2"], out=self.dH1[0])
                 torch.mm(self.dZ2[1], c16["W2"], out=self.dH1[1])
             ext.silu_bwd(self.dH1, self.Z1, self.dZ1)
-            ext.wgrad(self.dZ1[0], w.Xmb, ac.slab, ao["W1"], ao["b1"], self.H)
-            ext.wgrad(self.dZ1[1], w.Xmb, cc.slab, co["W1"], co["b1"], self.H)
+            if pair:
+                ext.wgrad_pair(self.dZ1[0], w.Xmb, ac.slab, ao["W1"], ao["b1"], self.H,
+                               self.dZ1[1], w.Xmb, cc.slab, co["W1"], co["b1"], self.H)
+            else:
+                ext.wgrad(self.dZ1[0], w.Xmb, ac.slab, ao["W1"], ao["b1"], self.H)
+                ext.wgrad(self.dZ1[1], w.Xmb, cc.slab, co["W1"], co["b1"], self.H)
             if prefetch:
                 # all reads of workspace set p are done (the W1 wgrads were
                 # the last); let the side stream refill it for mb+2, and
@@ -711,8 +730,14 @@ class FusedPPOEngine:
                     with torch.cuda.stream(gs):
                         gather_into(mb + 1, self.ws[q])
                         self.ev_ready[q].record(gs)
-            ext.slab_reduce(ac.slab, ac.grad16, ac.sqnorm, ac.step_t)
-            ext.slab_reduce(cc.slab, cc.grad16, cc.sqnorm, cc.step_t)
+            if pair:
+                # no zeroing pass: the wgrads store (never accumulate), so
+                # the next minibatch overwrites every element summed here
+                ext.slab_reduce_pair(ac.slab, ac.grad16, ac.sqnorm, ac.step_t,
+                                     cc.slab, cc.grad16, cc.sqnorm, cc.step_t)
+            else:
+                ext.slab_reduce(ac.slab, ac.grad16, ac.sqnorm, ac.step_t)
+                ext.slab_reduce(cc.slab, cc.grad16, cc.sqnorm, cc.step_t)
             # ---- ONE all-reduce over both chains' shared grad buffer,
             # then fused clip/Adam per chain (+ bf16 mirror refresh)
             if self.world > 1:

@@ -211,6 +211,14 @@ def main():
     def k_slab_reduce():
         ext.slab_reduce(ac.slab, ac.grad16, ac.sqnorm, ac.step_t)
 
+    def k_wgrad_pair():
+        ext.wgrad_pair(F.dZ2[0], F.H1[0], ac.slab, ac.offsets["W2"], ac.offsets["b2"], F.H,
+                       F.dZ2[1], F.H1[1], cc.slab, cc.offsets["W2"], cc.offsets["b2"], F.H)
+
+    def k_slab_reduce_pair():
+        ext.slab_reduce_pair(ac.slab, ac.grad16, ac.sqnorm, ac.step_t,
+                             cc.slab, cc.grad16, cc.sqnorm, cc.step_t)
+
     def k_dgrad():
         torch.mm(F.dZ2[0], a16["W2"], out=F.dH1[0])
 
@@ -242,6 +250,10 @@ def main():
     print(f"wgrad mm:           {timeit(k_wgrad, 50)*1e3:8.1f} us")
     print(f"wgrad custom:       {timeit(k_wgrad_custom, 50)*1e3:8.1f} us")
     print(f"slab_reduce:        {timeit(k_slab_reduce, 50)*1e3:8.1f} us")
+    print(f"wgrad_pair (W2):    {timeit(k_wgrad_pair, 50)*1e3:8.1f} us"
+          "  (both nets; replaces two of wgrad custom)")
+    print(f"slab_reduce_pair:   {timeit(k_slab_reduce_pair, 50)*1e3:8.1f} us"
+          "  (both chains; replaces two of slab_reduce)")
     print(f"dgrad mm:           {timeit(k_dgrad, 50)*1e3:8.1f} us")
     print(f"dgrad bmm stacked:  {timeit(k_dgrad_bmm, 50)*1e3:8.1f} us")
     print(f"head dgrads (2 mm): {timeit(k_head_dgrads, 50)*1e3:8.1f} us")
