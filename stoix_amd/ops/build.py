@@ -25,6 +25,7 @@ SOURCES = [
     str(CSRC / "rnn.hip"),
     str(CSRC / "snake.hip"),
     str(CSRC / "c51.hip"),
+    str(CSRC / "mcts.hip"),
 ]
 
 

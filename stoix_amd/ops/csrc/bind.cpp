@@ -138,6 +138,14 @@ void launch_c51_loss_fwd(const void*, const float*, const long*, const float*,
 void launch_c51_loss_bwd(const float*, long, const void*, const long*,
                          const float*, const float*, void*, int, int, int,
                          int, long, void*);
+void launch_mcts_select(const float*, const float*, const float*, const float*,
+                        const float*, const long*, const float*, const float*,
+                        long*, long*, int, int, int, float, void*);
+void launch_mcts_expand_backup(float*, float*, float*, float*, float*, long*,
+                               long*, long*, float*, float*, const long*,
+                               const long*, const float*, const float*,
+                               const float*, const float*, int, int, int, int,
+                               void*);
 }
 
 namespace {
@@ -873,6 +881,102 @@ void c51_loss_bwd(torch::Tensor grad_ce, torch::Tensor logits_tm1,
                       cur_stream());
 }
 
+// Argument checks shared by the two MCTS launchers (mcts.hip): the arena of
+// search/mcts.py, contiguous on one GPU, B trees x N node slots x A actions.
+struct MctsShape {
+  int64_t B, N, A;
+};
+
+void check_mcts_tensor(const torch::Tensor& t, const char* name,
+                       torch::ScalarType ty, const torch::Device& dev,
+                       std::initializer_list<int64_t> shape) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev && t.is_contiguous(), "mcts: ",
+              name, " must be a contiguous tensor on ", dev);
+  TORCH_CHECK(t.scalar_type() == ty, "mcts: ", name, " must be ", ty);
+  TORCH_CHECK(t.sizes() == torch::IntArrayRef(shape), "mcts: ", name,
+              " must have shape ", torch::IntArrayRef(shape), ", got ",
+              t.sizes());
+}
+
+MctsShape check_mcts_arena(const torch::Tensor& visit,
+                           const torch::Tensor& value_sum,
+                           const torch::Tensor& reward,
+                           const torch::Tensor& discount,
+                           const torch::Tensor& prior,
+                           const torch::Tensor& children,
+                           const torch::Tensor& min_q,
+                           const torch::Tensor& max_q) {
+  TORCH_CHECK(prior.dim() == 3, "mcts: prior must be [B, N, A]");
+  const int64_t B = prior.size(0), N = prior.size(1), A = prior.size(2);
+  TORCH_CHECK(N >= 1 && A >= 1, "mcts: the arena needs N >= 1 and A >= 1");
+  TORCH_CHECK(B * N * A < (int64_t(1) << 31) && B < (int64_t(1) << 31) - 256,
+              "mcts: arena too large for the kernels' int sizes");
+  const torch::Device dev = prior.device();
+  check_mcts_tensor(visit, "visit", torch::kFloat32, dev, {B, N});
+  check_mcts_tensor(value_sum, "value_sum", torch::kFloat32, dev, {B, N});
+  check_mcts_tensor(reward, "reward", torch::kFloat32, dev, {B, N});
+  check_mcts_tensor(discount, "discount", torch::kFloat32, dev, {B, N});
+  check_mcts_tensor(prior, "prior", torch::kFloat32, dev, {B, N, A});
+  check_mcts_tensor(children, "children", torch::kInt64, dev, {B, N, A});
+  check_mcts_tensor(min_q, "min_q", torch::kFloat32, dev, {B});
+  check_mcts_tensor(max_q, "max_q", torch::kFloat32, dev, {B});
+  return {B, N, A};
+}
+
+void mcts_select(torch::Tensor visit, torch::Tensor value_sum,
+                 torch::Tensor reward, torch::Tensor discount,
+                 torch::Tensor prior, torch::Tensor children,
+                 torch::Tensor min_q, torch::Tensor max_q, double c_puct,
+                 torch::Tensor sel_parent, torch::Tensor sel_action) {
+  const MctsShape s = check_mcts_arena(visit, value_sum, reward, discount,
+                                       prior, children, min_q, max_q);
+  const torch::Device dev = prior.device();
+  check_mcts_tensor(sel_parent, "sel_parent", torch::kInt64, dev, {s.B});
+  check_mcts_tensor(sel_action, "sel_action", torch::kInt64, dev, {s.B});
+  launch_mcts_select(visit.data_ptr<float>(), value_sum.data_ptr<float>(),
+                     reward.data_ptr<float>(), discount.data_ptr<float>(),
+                     prior.data_ptr<float>(), children.data_ptr<long>(),
+                     min_q.data_ptr<float>(), max_q.data_ptr<float>(),
+                     sel_parent.data_ptr<long>(), sel_action.data_ptr<long>(),
+                     (int)s.B, (int)s.N, (int)s.A, (float)c_puct,
+                     cur_stream());
+}
+
+void mcts_expand_backup(torch::Tensor visit, torch::Tensor value_sum,
+                        torch::Tensor reward, torch::Tensor discount,
+                        torch::Tensor prior, torch::Tensor children,
+                        torch::Tensor parent, torch::Tensor act_from_parent,
+                        torch::Tensor min_q, torch::Tensor max_q,
+                        torch::Tensor sel_parent, torch::Tensor sel_action,
+                        int64_t new_node, torch::Tensor reward_new,
+                        torch::Tensor discount_new, torch::Tensor prior_new,
+                        torch::Tensor value_new) {
+  const MctsShape s = check_mcts_arena(visit, value_sum, reward, discount,
+                                       prior, children, min_q, max_q);
+  const torch::Device dev = prior.device();
+  check_mcts_tensor(parent, "parent", torch::kInt64, dev, {s.B, s.N});
+  check_mcts_tensor(act_from_parent, "act_from_parent", torch::kInt64, dev,
+                    {s.B, s.N});
+  check_mcts_tensor(sel_parent, "sel_parent", torch::kInt64, dev, {s.B});
+  check_mcts_tensor(sel_action, "sel_action", torch::kInt64, dev, {s.B});
+  check_mcts_tensor(reward_new, "reward", torch::kFloat32, dev, {s.B});
+  check_mcts_tensor(discount_new, "discount", torch::kFloat32, dev, {s.B});
+  check_mcts_tensor(prior_new, "prior_new", torch::kFloat32, dev, {s.B, s.A});
+  check_mcts_tensor(value_new, "value", torch::kFloat32, dev, {s.B});
+  TORCH_CHECK(new_node >= 1 && new_node < s.N, "mcts: new_node ", new_node,
+              " is outside [1, ", s.N, ")");
+  launch_mcts_expand_backup(
+      visit.data_ptr<float>(), value_sum.data_ptr<float>(),
+      reward.data_ptr<float>(), discount.data_ptr<float>(),
+      prior.data_ptr<float>(), children.data_ptr<long>(),
+      parent.data_ptr<long>(), act_from_parent.data_ptr<long>(),
+      min_q.data_ptr<float>(), max_q.data_ptr<float>(),
+      sel_parent.data_ptr<long>(), sel_action.data_ptr<long>(),
+      reward_new.data_ptr<float>(), discount_new.data_ptr<float>(),
+      prior_new.data_ptr<float>(), value_new.data_ptr<float>(), (int)s.B,
+      (int)s.N, (int)s.A, (int)new_node, cur_stream());
+}
+
 }  // namespace
 
 void sumtree_update(torch::Tensor tree, torch::Tensor idx,
@@ -1040,6 +1144,10 @@ void snake_step(torch::Tensor grid, torch::Tensor head_r,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("mcts_select", &mcts_select,
+        "MCTS: PUCT descent of every tree to its expansion edge");
+  m.def("mcts_expand_backup", &mcts_expand_backup,
+        "MCTS: write the new node, link it and back its value up to the root");
   m.def("c51_loss_fwd", &c51_loss_fwd,
         "C51 categorical TD loss: softmax + fixed-order projection + CE");
   m.def("c51_loss_bwd", &c51_loss_bwd,
