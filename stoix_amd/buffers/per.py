@@ -69,9 +69,27 @@ class SumTree:
         return self.tree[1]
 
     @torch.no_grad()
-    def sample(self, batch_size: int, generator=None) -> Tensor:
-        """Stratified proportional sampling: batched tree descent."""
-        u = torch.rand(batch_size, device=self.device, generator=generator)
+    def sample(self, batch_size: int, generator=None, u: Tensor | None = None) -> Tensor:
+        """Stratified proportional sampling: batched tree descent.
+
+        Draw i takes the mass ``(i + u_i) * (total / batch_size)``; ``u``
+        (float32 in [0, 1), one per draw) is drawn here unless given.
+
+        The descent is guarded: go right iff ``(mass >= left and right > 0)
+        or left <= 0``. ``mass >= left`` alone can leave its stratum, when
+        the mass rounds to >= total or a rounded parent sum leaves
+        ``mass - left >= right``, and then runs right to a zero-priority
+        leaf or past ``n_items``. Every parent is fl32(left + right) of
+        non-negative children, so a positive node has a positive child on
+        the side taken and the walk from a positive root ends on a
+        positive-priority item. The HIP kernel does the same operations in
+        the same order."""
+        if u is None:
+            u = torch.rand(batch_size, device=self.device, generator=generator)
+        else:
+            u = u.to(device=self.device, dtype=torch.float32).contiguous()
+            if u.shape != (batch_size,):
+                raise ValueError(f"u has shape {tuple(u.shape)}, expected ({batch_size},)")
         if self._hip is not None:
             out = torch.empty(batch_size, dtype=torch.long, device=self.device)
             self._hip.sumtree_sample(self.tree, u, out, self.capacity,
@@ -83,7 +101,8 @@ class SumTree:
         for _ in range(self.depth):
             left = 2 * node
             left_sum = self.tree[left]
-            go_right = mass >= left_sum
+            right_sum = self.tree[left + 1]
+            go_right = ((mass >= left_sum) & (right_sum > 0)) | (left_sum <= 0)
             mass = torch.where(go_right, mass - left_sum, mass)
             node = torch.where(go_right, left + 1, left)
         return (node - self.capacity).clamp(0, self.n_items - 1)

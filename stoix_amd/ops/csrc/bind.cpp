@@ -236,10 +236,38 @@ void ant_reset(torch::Tensor state, int64_t seed, int64_t draw) {
                    (uint32_t)draw, cur_stream());
 }
 
+// The scan kernels index every operand as r_t's contiguous [T, B] matrix, so
+// each one has to be exactly that: on r_t's device, contiguous, of the
+// kernel's dtype and of r_t's shape. T * B is an int in the kernels.
+void scan_shape_check(const torch::Tensor& r_t) {
+  CHK(r_t, torch::kFloat32);
+  TORCH_CHECK(r_t.dim() == 2 && r_t.size(0) >= 1 && r_t.size(1) >= 1,
+              "scan: r_t must be a non-empty [T, B] matrix, got ", r_t.sizes());
+  TORCH_CHECK(r_t.numel() < (int64_t(1) << 31), "scan: T * B must fit an int");
+}
+
+void scan_operand_check(const torch::Tensor& t, const torch::Tensor& r_t,
+                        const char* name,
+                        torch::ScalarType ty = torch::kFloat32) {
+  TORCH_CHECK(t.is_cuda() && t.device() == r_t.device(), "scan: ", name,
+              " must be on r_t's GPU");
+  TORCH_CHECK(t.is_contiguous(), "scan: ", name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == ty, "scan: ", name, " must be ", ty);
+  TORCH_CHECK(t.sizes() == r_t.sizes(), "scan: ", name, " has shape ",
+              t.sizes(), ", r_t has ", r_t.sizes());
+}
+
 void gae(torch::Tensor r_t, torch::Tensor discount_t, torch::Tensor v_tm1,
          torch::Tensor v_t, torch::Tensor trunc_t, torch::Tensor adv_out,
          torch::Tensor target_out, double lambda_) {
-  CHK(r_t, torch::kFloat32);
+  scan_shape_check(r_t);
+  scan_operand_check(discount_t, r_t, "discount_t");
+  scan_operand_check(v_tm1, r_t, "v_tm1");
+  scan_operand_check(v_t, r_t, "v_t");
+  scan_operand_check(adv_out, r_t, "adv_out");
+  scan_operand_check(target_out, r_t, "target_out");
+  if (trunc_t.numel() > 0)
+    scan_operand_check(trunc_t, r_t, "trunc_t", torch::kUInt8);
   int T = r_t.size(0), B = r_t.size(1);
   const unsigned char* tr =
       trunc_t.numel() > 0 ? trunc_t.data_ptr<unsigned char>() : nullptr;
@@ -251,7 +279,10 @@ void gae(torch::Tensor r_t, torch::Tensor discount_t, torch::Tensor v_tm1,
 
 void lambda_returns(torch::Tensor r_t, torch::Tensor discount_t,
                     torch::Tensor v_t, torch::Tensor out, double lambda_) {
-  CHK(r_t, torch::kFloat32);
+  scan_shape_check(r_t);
+  scan_operand_check(discount_t, r_t, "discount_t");
+  scan_operand_check(v_t, r_t, "v_t");
+  scan_operand_check(out, r_t, "out");
   launch_lambda_returns(r_t.data_ptr<float>(), discount_t.data_ptr<float>(),
                         v_t.data_ptr<float>(), out.data_ptr<float>(),
                         r_t.size(0), r_t.size(1), (float)lambda_,
@@ -262,7 +293,13 @@ void vtrace(torch::Tensor v_tm1, torch::Tensor v_t, torch::Tensor r_t,
             torch::Tensor discount_t, torch::Tensor rho_tm1,
             torch::Tensor errors_out, torch::Tensor pg_adv_out, double lambda_,
             double clip_rho, double clip_pg_rho) {
-  CHK(r_t, torch::kFloat32);
+  scan_shape_check(r_t);
+  scan_operand_check(v_tm1, r_t, "v_tm1");
+  scan_operand_check(v_t, r_t, "v_t");
+  scan_operand_check(discount_t, r_t, "discount_t");
+  scan_operand_check(rho_tm1, r_t, "rho_tm1");
+  scan_operand_check(errors_out, r_t, "errors_out");
+  scan_operand_check(pg_adv_out, r_t, "pg_adv_out");
   launch_vtrace(v_tm1.data_ptr<float>(), v_t.data_ptr<float>(),
                 r_t.data_ptr<float>(), discount_t.data_ptr<float>(),
                 rho_tm1.data_ptr<float>(), errors_out.data_ptr<float>(),
@@ -274,7 +311,12 @@ void vtrace(torch::Tensor v_tm1, torch::Tensor v_t, torch::Tensor r_t,
 void offpolicy_returns(torch::Tensor q_t, torch::Tensor v_t, torch::Tensor r_t,
                        torch::Tensor discount_t, torch::Tensor c_t,
                        torch::Tensor out) {
-  CHK(r_t, torch::kFloat32);
+  scan_shape_check(r_t);
+  scan_operand_check(q_t, r_t, "q_t");
+  scan_operand_check(v_t, r_t, "v_t");
+  scan_operand_check(discount_t, r_t, "discount_t");
+  scan_operand_check(c_t, r_t, "c_t");
+  scan_operand_check(out, r_t, "out");
   launch_offpolicy_returns(q_t.data_ptr<float>(), v_t.data_ptr<float>(),
                            r_t.data_ptr<float>(), discount_t.data_ptr<float>(),
                            c_t.data_ptr<float>(), out.data_ptr<float>(),
@@ -979,11 +1021,22 @@ void mcts_expand_backup(torch::Tensor visit, torch::Tensor value_sum,
 
 }  // namespace
 
+void sumtree_tree_check(const torch::Tensor& tree, int64_t cap,
+                        int64_t depth) {
+  TORCH_CHECK(depth >= 0 && depth < 31 && cap == (int64_t(1) << depth),
+              "sumtree: cap ", cap, " is not 1 << depth (depth ", depth, ")");
+  TORCH_CHECK(tree.numel() == 2 * cap, "sumtree: tree holds ", tree.numel(),
+              " floats, expected 2 * cap = ", 2 * cap);
+}
+
 void sumtree_update(torch::Tensor tree, torch::Tensor idx,
                     torch::Tensor prio, int64_t cap, int64_t depth) {
   CHK(tree, torch::kFloat32);
   CHK(idx, torch::kInt64);
   CHK(prio, torch::kFloat32);
+  sumtree_tree_check(tree, cap, depth);
+  TORCH_CHECK(prio.numel() == idx.numel(), "sumtree_update: ", prio.numel(),
+              " priorities for ", idx.numel(), " indices");
   launch_sumtree_update(tree.data_ptr<float>(), idx.data_ptr<long>(),
                         prio.data_ptr<float>(), idx.numel(), (int)cap,
                         (int)depth, cur_stream());
@@ -994,6 +1047,14 @@ void sumtree_sample(torch::Tensor tree, torch::Tensor u, torch::Tensor out,
   CHK(tree, torch::kFloat32);
   CHK(u, torch::kFloat32);
   CHK(out, torch::kInt64);
+  sumtree_tree_check(tree, cap, depth);
+  TORCH_CHECK(n_items >= 1 && n_items <= cap, "sumtree_sample: n_items ",
+              n_items, " outside [1, cap = ", cap, "]");
+  TORCH_CHECK(out.numel() == u.numel(), "sumtree_sample: out holds ",
+              out.numel(), " slots for ", u.numel(), " draws");
+  // the kernel reads both children of a node as one 8-byte load
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(tree.data_ptr<float>()) % 8 == 0,
+              "sumtree_sample: tree must be 8-byte aligned");
   launch_sumtree_sample(tree.data_ptr<float>(), u.data_ptr<float>(),
                         out.data_ptr<long>(), u.numel(), (int)cap, (int)depth,
                         (int)n_items, cur_stream());

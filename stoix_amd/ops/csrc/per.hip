@@ -21,10 +21,15 @@
 //     launches; inside a captured graph each costs ~1.5 us boundary.
 //
 // Sample: stratified proportional descent — thread i draws mass
-// (i + u_i) * total / n and walks root->leaf in depth steps. The upper
+// (i + u_i) * (total / n) and walks root->leaf in depth guarded steps (see
+// sumtree_sample_kernel). The upper
 // tree levels are a few KB and stay L2/L1-resident, so the walk is
 // latency- not bandwidth-bound; one launch replaces ~depth torch gathers.
 #include "common.h"
+
+// The tree and the draws are compared bit for bit with the torch path, which
+// rounds after every operation: no FMA contraction in this file.
+#pragma clang fp contract(off)
 
 extern "C" __global__ void sumtree_update_single_kernel(
     float* __restrict__ tree, const long* __restrict__ idx,
@@ -84,21 +89,31 @@ extern "C" __global__ void sumtree_fix_level_kernel(
   tree[node] = tree[2 * node] + tree[2 * node + 1];
 }
 
+// Guarded descent: go right iff (mass >= left && right > 0) || left <= 0.
+// The plain rule `mass >= left` can walk off its stratum: (i + u) * seg may
+// round to >= total, and a rounded parent sum can leave mass - left >= right;
+// the walk then keeps right down to a leaf of priority 0 or beyond n_items.
+// Each parent is fl32(left + right) of non-negative children, so a positive
+// node has a positive child on the side the guard takes, and the walk from a
+// positive root ends on a positive leaf < n_items for every u and rounding.
+// SumTree.sample's torch path (buffers/per.py) runs the same operations in
+// the same order, so the two agree bit for bit. The children of a node are
+// adjacent and 8-byte aligned: one float2 load per level.
 extern "C" __global__ void sumtree_sample_kernel(
     const float* __restrict__ tree, const float* __restrict__ u,
     long* __restrict__ out, int n, int cap, int depth, int n_items) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const float2* __restrict__ children = reinterpret_cast<const float2*>(tree);
   float total = tree[1];
   float seg = total / (float)n;
   float mass = ((float)i + u[i]) * seg;
   long node = 1;
   for (int l = 0; l < depth; ++l) {
-    long left = 2 * node;
-    float ls = tree[left];
-    bool right = mass >= ls;
-    mass = right ? mass - ls : mass;
-    node = right ? left + 1 : left;
+    float2 c = children[node];  // c.x = tree[2 * node], c.y = tree[2 * node + 1]
+    bool right = (mass >= c.x && c.y > 0.0f) || c.x <= 0.0f;
+    mass = right ? mass - c.x : mass;
+    node = 2 * node + (right ? 1 : 0);
   }
   long item = node - (long)cap;
   if (item < 0) item = 0;

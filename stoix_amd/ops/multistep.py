@@ -29,6 +29,21 @@ import torch
 Tensor = torch.Tensor
 
 
+def _scan_operands(r_t: Tensor, *operands: Tensor):
+    """Operands of a HIP scan launch: each broadcast to ``r_t``'s shape and
+    laid out as a contiguous ``[T, N]`` matrix (N = the product of the
+    trailing dimensions), which is the only layout the kernels index."""
+    T = r_t.shape[0]
+    return [torch.broadcast_to(x, r_t.shape).reshape(T, -1).contiguous()
+            for x in (r_t, *operands)]
+
+
+def _scan_output(flat_r_t: Tensor) -> Tensor:
+    """A contiguous ``[T, N]`` output. ``empty_like`` is not used: it copies
+    the strides of a transposed input, and the kernels write row-major."""
+    return torch.empty(flat_r_t.shape, dtype=flat_r_t.dtype, device=flat_r_t.device)
+
+
 def batch_truncated_generalized_advantage_estimation(
     r_t: Tensor,
     discount_t: Tensor,
@@ -60,23 +75,17 @@ def batch_truncated_generalized_advantage_estimation(
         from stoix_amd import ops as _ops
 
         e = _ops.ext(required=True)
-        adv = torch.empty_like(r_t)
-        targets = torch.empty_like(r_t)
+        r, d, vm, vt = _scan_operands(r_t, discount_t, v_tm1, v_t)
+        adv = _scan_output(r)
+        targets = _scan_output(r)
         tr = (
-            truncation_t.to(torch.uint8).contiguous()
+            _scan_operands(r_t, truncation_t.to(torch.uint8))[1]
             if truncation_t is not None
             else torch.empty(0, dtype=torch.uint8, device=r_t.device)
         )
-        e.gae(
-            r_t.contiguous(),
-            discount_t.contiguous(),
-            v_tm1.contiguous(),
-            v_t.contiguous(),
-            tr,
-            adv,
-            targets,
-            float(lambda_),
-        )
+        e.gae(r, d, vm, vt, tr, adv, targets, float(lambda_))
+        adv = adv.reshape(r_t.shape)
+        targets = targets.reshape(r_t.shape)
         if standardize_advantages:
             adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
         return adv, targets
@@ -146,9 +155,10 @@ def batch_lambda_returns(
         from stoix_amd import ops as _ops
 
         e = _ops.ext(required=True)
-        out = torch.empty_like(r_t)
-        e.lambda_returns(r_t.contiguous(), discount_t.contiguous(), v_t.contiguous(), out, float(lambda_))
-        return out
+        r, d, vt = _scan_operands(r_t, discount_t, v_t)
+        out = _scan_output(r)
+        e.lambda_returns(r, d, vt, out, float(lambda_))
+        return out.reshape(r_t.shape)
     out = torch.empty_like(r_t)
     acc = v_t[-1]
     for t in range(T - 1, -1, -1):
@@ -188,12 +198,10 @@ def batch_general_off_policy_returns_from_q_and_v(
         from stoix_amd import ops as _ops
 
         e = _ops.ext(required=True)
-        out = torch.empty_like(r_t)
-        e.offpolicy_returns(
-            q_t.contiguous(), v_t.contiguous(), r_t.contiguous(),
-            discount_t.contiguous(), c_t.contiguous(), out,
-        )
-        return out
+        r, q, vt, d, c = _scan_operands(r_t, q_t, v_t, discount_t, c_t)
+        out = _scan_output(r)
+        e.offpolicy_returns(q, vt, r, d, c, out)
+        return out.reshape(r_t.shape)
     out = torch.empty_like(r_t)
     g = r_t[T - 1] + discount_t[T - 1] * v_t[T - 1]
     out[T - 1] = g
@@ -294,13 +302,15 @@ def vtrace_td_error_and_advantage(
         from stoix_amd import ops as _ops
 
         e = _ops.ext(required=True)
-        errors = torch.empty_like(r_t)
-        pg_adv = torch.empty_like(r_t)
+        r, vm, vt, d, rho = _scan_operands(r_t, v_tm1, v_t, discount_t, rho_tm1)
+        errors = _scan_output(r)
+        pg_adv = _scan_output(r)
         e.vtrace(
-            v_tm1.contiguous(), v_t.contiguous(), r_t.contiguous(),
-            discount_t.contiguous(), rho_tm1.contiguous(), errors, pg_adv,
+            vm, vt, r, d, rho, errors, pg_adv,
             float(lambda_), float(clip_rho_threshold), float(clip_pg_rho_threshold),
         )
+        errors = errors.reshape(r_t.shape)
+        pg_adv = pg_adv.reshape(r_t.shape)
         vs_t = torch.cat([errors[1:] + v_tm1[1:], v_t[-1:]], dim=0)
         q_estimate = r_t + discount_t * vs_t
         return errors, pg_adv, q_estimate

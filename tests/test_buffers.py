@@ -224,3 +224,98 @@ def test_trajectory_windows_valid_under_random_adds_property():
             assert torch.all((gt[:, 0] - oldest) % period == 0), seed
 
     run()
+
+
+# ------------------------------------------- guarded descent (adversarial u)
+
+
+def _tree_with(n_items, seed):
+    from sumtree_oracle import priorities
+
+    tree = SumTree(n_items)
+    prio = priorities(n_items, seed)
+    tree.set(torch.arange(n_items), prio)
+    return tree, prio
+
+
+def test_sum_tree_descent_lands_on_positive_items_for_adversarial_u():
+    """Properties (b) and (c) of tests/sumtree_oracle.py for the torch
+    descent, with u at the ends of every stratum (0 and 1 - 2**-24, which
+    torch.rand can return) as well as random, on trees with interior zero
+    runs and a zero tail. The unguarded rule ``mass >= left`` returned a
+    zero-priority slot from the last stratum at u = 1 - 2**-24 in about
+    0.5 % of such draws; uniform random u never shows it."""
+    from sumtree_oracle import (SAMPLE_BATCHES, TREE_SIZES, adversarial_u,
+                                assert_draws_valid, assert_tree_consistent)
+
+    worst = 0.0
+    for n_items in TREE_SIZES + (100_000,):
+        for seed in range(3):
+            tree, prio = _tree_with(n_items, seed)
+            assert_tree_consistent(tree.tree, tree.capacity, prio, f"n_items={n_items}")
+            for n in SAMPLE_BATCHES + (200, 1000):
+                for name, u in adversarial_u(n, seed).items():
+                    out = tree.sample(n, u=u)
+                    worst = max(worst, assert_draws_valid(
+                        tree.tree, tree.capacity, tree.depth, n_items, u, out,
+                        f"n_items={n_items} seed={seed} batch={n} u={name}"))
+    print(f"largest distance outside the leaf interval: {worst:.4f} delta")
+
+
+def test_sum_tree_sample_takes_the_given_u():
+    tree, prio = _tree_with(1000, 0)
+    u = torch.rand(64, generator=torch.Generator().manual_seed(5))
+    a = tree.sample(64, u=u)
+    assert torch.equal(a, tree.sample(64, u=u.double()))  # converted to float32
+    # drawn from the generator when u is not given: same stream, same result
+    b = tree.sample(64, torch.Generator().manual_seed(5))
+    assert torch.equal(a, b)
+    import pytest
+
+    with pytest.raises(ValueError):
+        tree.sample(64, u=u[:63])
+
+
+def test_prioritised_buffer_never_samples_behind_the_write_head(monkeypatch):
+    """The slots straight behind the write head have priority 0: a window
+    starting there would cross the head. With u = 1 - 2**-24 the last
+    stratum's mass can round up to the total, and the unguarded descent then
+    ran right down to such a slot: its IS weight (1 / 1e-12) ** beta is the
+    batch maximum, and after the normalisation every other row's weight is
+    close to 0. Every window must lie in written data, contiguous in time,
+    and every weight must stay positive."""
+    from sumtree_oracle import U_MAX
+
+    rows, t_max, seq, t_block = 2, 32, 4, 8
+    hits = 0
+    for seed in range(4):
+        buf = PrioritisedBuffer(add_batch_size=rows, max_length_time_axis=t_max,
+                                sample_sequence_length=seq, seed=seed)
+        g = torch.Generator().manual_seed(seed)
+        glob = 0
+        for _ in range(2 + seed):  # the head ends inside the ring, or wraps
+            # cell value = global time + 1; unwritten storage stays 0
+            block = (glob + 1 + torch.arange(t_block)).float().expand(rows, -1)
+            buf.add({"t": block.contiguous()})
+            glob += t_block
+        leaves = buf.tree.tree[buf.tree.capacity: buf.tree.capacity + buf.n_slots]
+        live = (leaves > 0).nonzero().flatten()
+        buf.set_priorities(live, torch.rand(live.numel(), generator=g) * 5)
+        leaves = buf.tree.tree[buf.tree.capacity: buf.tree.capacity + buf.n_slots]
+        head = buf.t_ptr
+        behind = [(head - 1 - k) % t_max for k in range(seq - 1)]
+        assert (leaves.view(rows, t_max)[:, behind] == 0).all()
+
+        monkeypatch.setattr(torch, "rand", lambda n, device=None, generator=None:
+                            torch.full((n,), U_MAX, device=device))
+        for batch in range(1, 257):
+            s = buf.sample(batch)
+            w = s["t"]
+            assert (w.min() >= 1) and (w.diff(dim=1) == 1).all(), (
+                f"seed {seed} batch {batch}: a window crosses the write head: "
+                f"slots {s['_slots'][(w.diff(dim=1) != 1).any(1) | (w.min(1).values < 1)].tolist()}")
+            assert (leaves[s["_slots"]] > 0).all()
+            assert float(s["_weights"].min()) > 0
+            hits += 1
+        monkeypatch.undo()
+    assert hits == 4 * 256

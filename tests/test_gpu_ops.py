@@ -343,7 +343,7 @@ def test_hip_env_step_outputs_are_stable_across_steps(ext):
 @requires_gpu
 def test_sumtree_hip_update_matches_cpu_reference(ext):
     """HIP sumtree_update (scatter + per-level ancestor repair) vs the
-    torch fallback on CPU, including the multi-launch path (n > 4096) and
+    torch fallback on CPU, including the multi-launch path (n > 8192) and
     duplicate indices."""
     from stoix_amd.buffers.per import SumTree
 
