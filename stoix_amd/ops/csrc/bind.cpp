@@ -93,6 +93,17 @@ int launch_wgrad_pair(const void*, const void*, float*, long, long, long, int,
 void launch_slab_reduce_pair(const float*, void*, long, long, float*, long*,
                              const float*, void*, long, long, float*, long*,
                              void*);
+int launch_linear_silu_pair(const void*, const void*, const float*, void*,
+                            void*, const void*, const float*, void*, void*,
+                            int, int, int, void*);
+void launch_slab_reduce_norm_pair(const float*, void*, long, long, float*,
+                                  long*, unsigned int*, const float*, void*,
+                                  long, long, float*, long*, unsigned int*,
+                                  void*);
+void launch_adam_pair(float*, const void*, float*, float*, const float*,
+                      const long*, void*, long, float, float*, const void*,
+                      float*, float*, const float*, const long*, void*, long,
+                      float, float, float, float, float, float, void*);
 void launch_sumtree_update(float*, const long*, const float*, long, int, int,
                            void*);
 void launch_sumtree_sample(const float*, const float*, long*, long, int, int,
@@ -590,6 +601,44 @@ void linear_silu(torch::Tensor X, torch::Tensor W, torch::Tensor bias,
                      Z.data_ptr(), h, S, K, N, (int)do_silu, cur_stream());
 }
 
+// Both nets' layer-1 Linear+SiLU in one launch over a shared X. Returns
+// false, with nothing launched, for a shape the paired kernel does not take
+// (S or N not a multiple of 128): the caller then runs linear_silu per net.
+bool linear_silu_pair(torch::Tensor X, torch::Tensor W_a, torch::Tensor b_a,
+                      torch::Tensor Z_a, torch::Tensor H_a, torch::Tensor W_c,
+                      torch::Tensor b_c, torch::Tensor Z_c,
+                      torch::Tensor H_c) {
+  CHK(X, torch::kBFloat16);
+  CHK(W_a, torch::kBFloat16);
+  CHK(W_c, torch::kBFloat16);
+  CHK(b_a, torch::kFloat32);
+  CHK(b_c, torch::kFloat32);
+  CHK(Z_a, torch::kBFloat16);
+  CHK(H_a, torch::kBFloat16);
+  CHK(Z_c, torch::kBFloat16);
+  CHK(H_c, torch::kBFloat16);
+  TORCH_CHECK(X.dim() == 2 && W_a.dim() == 2 && W_c.dim() == 2,
+              "linear_silu_pair: X and W must be 2-D");
+  const int64_t S = X.size(0), K = X.size(1), N = W_a.size(0);
+  TORCH_CHECK(W_a.size(1) == K && W_c.size(0) == N && W_c.size(1) == K,
+              "linear_silu_pair: the two nets' weight shapes differ");
+  TORCH_CHECK(b_a.numel() == N && b_c.numel() == N,
+              "linear_silu_pair: bias length");
+  TORCH_CHECK(Z_a.numel() == S * N && H_a.numel() == S * N &&
+                  Z_c.numel() == S * N && H_c.numel() == S * N,
+              "linear_silu_pair: outputs must hold S * N elements");
+  TORCH_CHECK(K > 0 && K % 32 == 0,
+              "linear_silu_pair: K must be a multiple of 32");
+  for (const torch::Tensor* t : {&X, &W_a, &W_c, &Z_a, &H_a, &Z_c, &H_c})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "linear_silu_pair: operands must be 16-byte aligned");
+  return launch_linear_silu_pair(
+             X.data_ptr(), W_a.data_ptr(), b_a.data_ptr<float>(),
+             Z_a.data_ptr(), H_a.data_ptr(), W_c.data_ptr(),
+             b_c.data_ptr<float>(), Z_c.data_ptr(), H_c.data_ptr(), (int)S,
+             (int)K, (int)N, cur_stream()) == 0;
+}
+
 void silu_fwd(torch::Tensor z, torch::Tensor h) {
   CHK(z, torch::kBFloat16);
   TORCH_CHECK(z.numel() % 8 == 0, "silu_fwd needs numel % 8 == 0");
@@ -807,6 +856,103 @@ void slab_reduce_pair(torch::Tensor slab0, torch::Tensor grad0,
                           slab1.data_ptr<float>(), grad1.data_ptr(),
                           slab1.size(1), grad1.numel(), sq1, st1,
                           cur_stream());
+}
+
+// The largest chain the two-launch tail takes: beyond it the norm kernel of
+// fused_adam_bf16 (2048 blocks of 256 threads, one 8-vector per thread)
+// goes grid-stride and the order of its adds is another one.
+constexpr int64_t kTailMaxN = 2048LL * 256 * 8;
+
+// slab_reduce_pair plus each chain's squared gradient norm, left in
+// sqnorm[0] with the bit pattern fused_adam_bf16's ordered norm gives.
+// sqnorm needs 1 + ceil(n / 512) floats, counter is one int32 that is zero
+// between calls.
+void slab_reduce_norm_pair(torch::Tensor slab0, torch::Tensor grad0,
+                           torch::Tensor sqnorm0, torch::Tensor step0,
+                           torch::Tensor counter0, torch::Tensor slab1,
+                           torch::Tensor grad1, torch::Tensor sqnorm1,
+                           torch::Tensor step1, torch::Tensor counter1) {
+  CHK(slab0, torch::kFloat32);
+  CHK(grad0, torch::kBFloat16);
+  CHK(sqnorm0, torch::kFloat32);
+  CHK(step0, torch::kInt64);
+  CHK(counter0, torch::kInt32);
+  CHK(slab1, torch::kFloat32);
+  CHK(grad1, torch::kBFloat16);
+  CHK(sqnorm1, torch::kFloat32);
+  CHK(step1, torch::kInt64);
+  CHK(counter1, torch::kInt32);
+  TORCH_CHECK(slab0.dim() == 2 && slab0.size(0) == 64 && slab1.dim() == 2 &&
+                  slab1.size(0) == 64,
+              "slab_reduce_norm_pair: slabs must be [64, n]");
+  const int64_t n0 = grad0.numel(), n1 = grad1.numel();
+  TORCH_CHECK(n0 >= 1 && n1 >= 1 && n0 <= slab0.size(1) && n1 <= slab1.size(1),
+              "slab_reduce_norm_pair: grad empty or longer than a slab image");
+  TORCH_CHECK(n0 <= kTailMaxN && n1 <= kTailMaxN,
+              "slab_reduce_norm_pair: chain too long for the ordered norm");
+  TORCH_CHECK(sqnorm0.numel() >= 1 + (n0 + 511) / 512 &&
+                  sqnorm1.numel() >= 1 + (n1 + 511) / 512,
+              "slab_reduce_norm_pair: sqnorm needs 1 + ceil(n / 512) floats");
+  TORCH_CHECK(step0.numel() == 1 && step1.numel() == 1 &&
+                  counter0.numel() == 1 && counter1.numel() == 1,
+              "slab_reduce_norm_pair: step_t and counter hold one element");
+  launch_slab_reduce_norm_pair(
+      slab0.data_ptr<float>(), grad0.data_ptr(), slab0.size(1), n0,
+      sqnorm0.data_ptr<float>(), step0.data_ptr<long>(),
+      (unsigned int*)counter0.data_ptr<int>(), slab1.data_ptr<float>(),
+      grad1.data_ptr(), slab1.size(1), n1, sqnorm1.data_ptr<float>(),
+      step1.data_ptr<long>(), (unsigned int*)counter1.data_ptr<int>(),
+      cur_stream());
+}
+
+// Both chains' clip + Adam + bf16 mirror in one launch, reading the
+// finished norm from sqnorm[0] (slab_reduce_norm_pair).
+void adam_pair(torch::Tensor param0, torch::Tensor grad0, torch::Tensor m0,
+               torch::Tensor v0, torch::Tensor sqnorm0, torch::Tensor step0,
+               torch::Tensor param_bf16_0, double lr0, torch::Tensor param1,
+               torch::Tensor grad1, torch::Tensor m1, torch::Tensor v1,
+               torch::Tensor sqnorm1, torch::Tensor step1,
+               torch::Tensor param_bf16_1, double lr1, double beta1,
+               double beta2, double eps, double max_norm, double grad_scale) {
+  CHK(param0, torch::kFloat32);
+  CHK(grad0, torch::kBFloat16);
+  CHK(m0, torch::kFloat32);
+  CHK(v0, torch::kFloat32);
+  CHK(sqnorm0, torch::kFloat32);
+  CHK(step0, torch::kInt64);
+  CHK(param1, torch::kFloat32);
+  CHK(grad1, torch::kBFloat16);
+  CHK(m1, torch::kFloat32);
+  CHK(v1, torch::kFloat32);
+  CHK(sqnorm1, torch::kFloat32);
+  CHK(step1, torch::kInt64);
+  const int64_t n0 = param0.numel(), n1 = param1.numel();
+  TORCH_CHECK(grad0.numel() == n0 && m0.numel() == n0 && v0.numel() == n0 &&
+                  grad1.numel() == n1 && m1.numel() == n1 && v1.numel() == n1,
+              "adam_pair: param, grad and moments must have one length");
+  TORCH_CHECK(sqnorm0.numel() >= 1 && sqnorm1.numel() >= 1 &&
+                  step0.numel() == 1 && step1.numel() == 1,
+              "adam_pair: sqnorm and step_t must not be empty");
+  void* pbf0 = nullptr;
+  void* pbf1 = nullptr;
+  if (param_bf16_0.numel() > 0) {
+    CHK(param_bf16_0, torch::kBFloat16);
+    TORCH_CHECK(param_bf16_0.numel() == n0, "adam_pair: bf16 mirror length");
+    pbf0 = param_bf16_0.data_ptr();
+  }
+  if (param_bf16_1.numel() > 0) {
+    CHK(param_bf16_1, torch::kBFloat16);
+    TORCH_CHECK(param_bf16_1.numel() == n1, "adam_pair: bf16 mirror length");
+    pbf1 = param_bf16_1.data_ptr();
+  }
+  launch_adam_pair(param0.data_ptr<float>(), grad0.data_ptr(),
+                   m0.data_ptr<float>(), v0.data_ptr<float>(),
+                   sqnorm0.data_ptr<float>(), step0.data_ptr<long>(), pbf0, n0,
+                   (float)lr0, param1.data_ptr<float>(), grad1.data_ptr(),
+                   m1.data_ptr<float>(), v1.data_ptr<float>(),
+                   sqnorm1.data_ptr<float>(), step1.data_ptr<long>(), pbf1, n1,
+                   (float)lr1, (float)beta1, (float)beta2, (float)eps,
+                   (float)max_norm, (float)grad_scale, cur_stream());
 }
 
 void bump_add(torch::Tensor draw_buf, int64_t n) {
@@ -1274,6 +1420,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("db_off1"), py::arg("n_valid1"), py::arg("variant") = -1);
   m.def("slab_reduce_pair", &slab_reduce_pair,
         "both chains' slabs -> flat bf16 grads, slabs left un-zeroed");
+  m.def("linear_silu_pair", &linear_silu_pair,
+        "both nets' Linear(+bias)+SiLU forward over one X, row-contiguous "
+        "stores; false = shape not taken, nothing launched");
+  m.def("slab_reduce_norm_pair", &slab_reduce_norm_pair,
+        "slab_reduce_pair + each chain's ordered squared grad norm");
+  m.def("adam_pair", &adam_pair,
+        "both chains' clip + Adam + bf16 mirror in one launch");
+  m.attr("TAIL_MAX_N") = kTailMaxN;
   m.def("bump_add", &bump_add, "add N to a device RNG draw counter");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
 }

@@ -16,7 +16,8 @@
 //     per sample row);
 //   * linear_silu, silu fwd/bwd + gather kernels: the epilogue/prologue
 //     glue so the update phase is GEMM (hipBLASLt MFMA) + a handful of
-//     fused kernels;
+//     fused kernels; linear_silu_pair is the layer-1 forward of both nets
+//     in one launch, stored row-contiguous through LDS;
 //   * silu_heads_fwd / heads_bwd_silu: the layer-2 SiLU passes of the
 //     update with the narrow head GEMMs (N=16/1 forward, K=16/1 backward)
 //     formed from the tile the pass already holds.
@@ -800,6 +801,189 @@ extern "C" void launch_linear_silu(const void* X, const void* W,
                        (const bf16_t*)W, bias, (bf16_t*)Z, (bf16_t*)H, S, K,
                        N);
   }
+}
+
+// ------------------------- both nets' layer-1 Linear+SiLU in one launch
+//
+// Same result as linear_silu_kernel<true>, bit for bit (one fp32
+// accumulator chain per 16x16 tile, k-steps ascending, z = acc + fp32 bias,
+// Z = bf16(z), H = bf16(silu(z))), for two nets that share X (blockIdx.z
+// picks the net). What differs is how the tile leaves the workgroup. The
+// old epilogue stores single bf16 elements from the accumulator layout
+// (one instruction = 4 rows x 32 B, 128 stores per lane), which is what
+// the kernel's time goes to at K = 32. Here
+//  * the MFMA operands are swapped (A = the W fragment, B = the X
+//    fragment; the products and their k order are the same), so a lane
+//    holds 4 CONSECUTIVE columns of one row: acc[mi][nj][r] is
+//    (row mi*16 + (lane&15), column nj*16 + (lane>>4)*4 + r);
+//  * each wave packs its 64x64 quadrant into a wave-private LDS tile with
+//    8-byte writes and reads it back as 16 bytes per lane, 8 lanes per
+//    128-byte row segment, so every global store instruction writes eight
+//    full 128-byte lines. No workgroup barrier in the epilogue.
+//
+// LDS tile image: 64 rows of 128 B, no padding. The 16-byte chunk c of row
+// R sits at chunk c ^ (R & 7), and rows with bit 3 set keep the two 8-byte
+// halves of every chunk swapped. Writes (ds_write_b64: groups of 16
+// consecutive lanes = 16 rows of one 8-byte column, banks (a/4) % 32): the
+// row pitch is 0 mod 32 banks, the XOR spreads rows R & 7 over the eight
+// 4-bank slots and the half swap separates R from R + 8, so the 16 lanes
+// tile the 32 banks. Reads (ds_read_b128: 16-lane groups holding half-rows
+// of four consecutive rows, banks (a/4) % 64): rows alternate between the
+// two 128-byte halves of the bank row and the XOR permutes chunks only
+// inside a half (R & 7 < 4) or swaps the halves (R & 7 >= 4), so each group
+// covers the 16 slots once. The half swap is undone in registers; which
+// rows need it is known at compile time (odd 8-row steps).
+//
+// The tile aliases the X staging buffers: one barrier between the last
+// MFMA and the first epilogue write.
+struct LinSiluNet {
+  const bf16_t* W;    // [N, K] row-major
+  const float* bias;  // [N]
+  bf16_t* Z;          // [S, N]
+  bf16_t* H;          // [S, N]
+};
+
+#define LSP_TILE_BYTES (64 * 128)
+
+DEV_INLINE void wave_lds_sync();  // defined with the fused head kernels below
+
+// One wave's 64x64 tile of `acc` (+ SiLU when ACT) -> LDS image -> `out`.
+template <bool ACT>
+DEV_INLINE void lsp_store_tile(const f32x4 (&acc)[4][4], unsigned char* tile,
+                               bf16_t* __restrict__ out, int N, int lane) {
+  const int i = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      bf16x4 v;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float z = acc[mi][nj][r];
+        v[r] = f2bf(ACT ? silu_f(z) : z);
+      }
+      const int chunk = (nj * 2 + (g >> 1)) ^ (i & 7);
+      const int half = (g & 1) ^ (i >> 3);
+      *reinterpret_cast<bf16x4*>(tile + (mi * 16 + i) * 128 + chunk * 16 +
+                                 half * 8) = v;
+    }
+  }
+  wave_lds_sync();
+  const int r8 = lane >> 3, c = lane & 7;
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int R = it * 8 + r8;
+    const bf16x8 t = *reinterpret_cast<const bf16x8*>(tile + R * 128 +
+                                                      ((c ^ r8) * 16));
+    const bf16x8 v = (it & 1)
+                         ? __builtin_shufflevector(t, t, 4, 5, 6, 7, 0, 1, 2, 3)
+                         : t;
+    *reinterpret_cast<bf16x8*>(out + (long)R * N + c * 8) = v;
+  }
+  wave_lds_sync();
+}
+
+__launch_bounds__(256, 2) __global__ void linear_silu_pair_kernel(
+    const bf16_t* __restrict__ X,  // [S, K], shared by both nets
+    LinSiluNet net0, LinSiluNet net1, int S, int K, int N) {
+  constexpr int A_BYTES = 2 * LSF_BM * (LSF_BK + LSF_APAD) * 2;
+  constexpr int T_BYTES = 4 * LSP_TILE_BYTES;
+  __shared__ alignas(16) unsigned char smem[A_BYTES > T_BYTES ? A_BYTES
+                                                               : T_BYTES];
+  typedef bf16_t ATile[LSF_BM][LSF_BK + LSF_APAD];
+  ATile* A = reinterpret_cast<ATile*>(smem);
+  const LinSiluNet net = blockIdx.z ? net1 : net0;
+  const bf16_t* __restrict__ W = net.W;
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int m0 = blockIdx.x * LSF_BM;
+  const int n_blk = blockIdx.y * 128;
+  const int wm = (wid >> 1) * 64;
+  const int wn = (wid & 1) * 64;
+  const int KS = K / LSF_BK;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  // as in linear_silu_kernel: 128x32 bf16 per k-step, 2 16-B pieces/thread
+  auto stage = [&](int ks, int pp) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      int flat = q * 256 + threadIdx.x;
+      int row = flat >> 2;
+      int kh = (flat & 3) * 8;
+      *reinterpret_cast<bf16x8*>(&A[pp][row][kh]) =
+          *reinterpret_cast<const bf16x8*>(X + (long)(m0 + row) * K +
+                                           ks * LSF_BK + kh);
+    }
+  };
+
+  stage(0, 0);
+  const int xrow_base = wm + (lane & 15);
+  const int ak0 = (lane >> 4) * 8;
+  for (int ks = 0; ks < KS; ++ks) {
+    __syncthreads();
+    if (ks + 1 < KS) stage(ks + 1, (ks + 1) & 1);
+    bf16x8 w[4];
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+      int n = n_blk + wn + nj * 16 + (lane & 15);
+      w[nj] = *reinterpret_cast<const bf16x8*>(W + (long)n * K +
+                                               ks * LSF_BK + ak0);
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const bf16x8 x = *reinterpret_cast<const bf16x8*>(
+          &A[ks & 1][xrow_base + mi * 16][ak0]);
+#pragma unroll
+      for (int nj = 0; nj < 4; ++nj) {
+        // W fragment as the A operand: the tile comes out transposed, four
+        // consecutive columns of one row per lane
+        acc[mi][nj] = MFMA_BF16_16x16x32(w[nj], x, acc[mi][nj], 0, 0, 0);
+      }
+    }
+  }
+
+  // z = acc + bias, in place
+  const int g = lane >> 4;
+#pragma unroll
+  for (int nj = 0; nj < 4; ++nj) {
+    const float* bp = net.bias + n_blk + wn + nj * 16 + g * 4;
+    const float b0 = bp[0], b1 = bp[1], b2 = bp[2], b3 = bp[3];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      acc[mi][nj][0] += b0;
+      acc[mi][nj][1] += b1;
+      acc[mi][nj][2] += b2;
+      acc[mi][nj][3] += b3;
+    }
+  }
+
+  __syncthreads();  // every wave is done with the staged X
+  unsigned char* tile = smem + wid * LSP_TILE_BYTES;
+  const long o = (long)(m0 + wm) * N + n_blk + wn;
+  lsp_store_tile<false>(acc, tile, net.Z + o, N, lane);
+  lsp_store_tile<true>(acc, tile, net.H + o, N, lane);
+}
+
+// Returns 0 after the launch, 1 for a shape the kernel does not take.
+extern "C" int launch_linear_silu_pair(const void* X, const void* W0,
+                                       const float* b0, void* Z0, void* H0,
+                                       const void* W1, const float* b1,
+                                       void* Z1, void* H1, int S, int K, int N,
+                                       void* stream) {
+  if (S <= 0 || S % LSF_BM != 0 || N <= 0 || N % 128 != 0 || K <= 0 ||
+      K % LSF_BK != 0)
+    return 1;
+  LinSiluNet n0{(const bf16_t*)W0, b0, (bf16_t*)Z0, (bf16_t*)H0};
+  LinSiluNet n1{(const bf16_t*)W1, b1, (bf16_t*)Z1, (bf16_t*)H1};
+  dim3 grid(S / LSF_BM, N / 128, 2), block(256);
+  hipLaunchKernelGGL(linear_silu_pair_kernel, grid, block, 0,
+                     (hipStream_t)stream, (const bf16_t*)X, n0, n1, S, K, N);
+  return 0;
 }
 
 // ------------------------------------------------------- update-phase glue

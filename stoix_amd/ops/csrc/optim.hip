@@ -215,6 +215,75 @@ extern "C" void launch_fused_adam_bf16(float* param, const void* grad,
                      beta2, eps, max_norm, grad_scale, n_partials);
 }
 
+// Both chains' clip + Adam in one launch (blockIdx.y picks the chain), for
+// the two-launch optimiser tail: slab_reduce_norm_pair (wgrad.hip) has left
+// the finished squared norm in sqnorm[0], so this is
+// adam_update_bf16_kernel's n_partials == 0 form, element for element.
+struct AdamChain {
+  float* param;
+  const opt_bf16* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  const float* sqnorm;
+  const long* step_t;
+  opt_bf16* param_bf16;  // or null
+  long n;
+  float lr;
+};
+
+extern "C" __global__ void adam_pair_kernel(AdamChain c0, AdamChain c1,
+                                            float beta1, float beta2,
+                                            float eps, float max_norm,
+                                            float grad_scale) {
+  const AdamChain c = blockIdx.y ? c1 : c0;
+  float* __restrict__ param = c.param;
+  const opt_bf16* __restrict__ grad = c.grad;
+  float* __restrict__ exp_avg = c.exp_avg;
+  float* __restrict__ exp_avg_sq = c.exp_avg_sq;
+  opt_bf16* __restrict__ param_bf16 = c.param_bf16;
+  const long n = c.n;
+  const float lr = c.lr;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  float clip = grad_scale;
+  if (max_norm > 0.0f) {
+    float sq = *c.sqnorm;
+    float norm = sqrtf(sq) * grad_scale;
+    if (norm > max_norm) clip = grad_scale * max_norm / (norm + 1e-6f);
+  }
+  long t = *c.step_t;
+  float bc1 = 1.0f - powf(beta1, (float)t);
+  float bc2 = 1.0f - powf(beta2, (float)t);
+  for (; i < n; i += stride) {
+    float g = (float)grad[i] * clip;
+    float m = exp_avg[i] = beta1 * exp_avg[i] + (1.0f - beta1) * g;
+    float v = exp_avg_sq[i] = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;
+    float p = param[i] - lr * (m / bc1) / (sqrtf(v / bc2) + eps);
+    param[i] = p;
+    if (param_bf16) param_bf16[i] = (opt_bf16)p;
+  }
+}
+
+extern "C" void launch_adam_pair(
+    float* param0, const void* grad0, float* exp_avg0, float* exp_avg_sq0,
+    const float* sqnorm0, const long* step0, void* param_bf16_0, long n0,
+    float lr0, float* param1, const void* grad1, float* exp_avg1,
+    float* exp_avg_sq1, const float* sqnorm1, const long* step1,
+    void* param_bf16_1, long n1, float lr1, float beta1, float beta2,
+    float eps, float max_norm, float grad_scale, void* stream) {
+  AdamChain c0{param0, (const opt_bf16*)grad0, exp_avg0, exp_avg_sq0, sqnorm0,
+               step0, (opt_bf16*)param_bf16_0, n0, lr0};
+  AdamChain c1{param1, (const opt_bf16*)grad1, exp_avg1, exp_avg_sq1, sqnorm1,
+               step1, (opt_bf16*)param_bf16_1, n1, lr1};
+  int threads = 256;
+  long nmax = n0 > n1 ? n0 : n1;
+  long want = (nmax + threads - 1) / threads;
+  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
+  hipLaunchKernelGGL(adam_pair_kernel, dim3(blocks, 2), dim3(threads), 0,
+                     (hipStream_t)stream, c0, c1, beta1, beta2, eps, max_norm,
+                     grad_scale);
+}
+
 // polyak: target <- tau * online + (1 - tau) * target (ff_dqn.py:207-209)
 extern "C" __global__ void polyak_kernel(const float* __restrict__ online,
                                          float* __restrict__ target,

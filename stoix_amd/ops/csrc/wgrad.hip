@@ -444,6 +444,141 @@ extern "C" __launch_bounds__(256) __global__ void slab_reduce_pair_kernel(
   }
 }
 
+// slab_reduce_pair_kernel plus the squared gradient norm of each chain, so
+// that the optimiser tail is this launch and adam_pair (optim.hip). It
+// leaves in sqnorm[0] the very float that grad_sqnorm_bf16_kernel (ordered
+// partials) and adam_update_bf16_kernel's sum of them produce, which fixes
+// the order of the float adds:
+//   * per group of 8 consecutive elements, acc = 0; acc += x_j * x_j in
+//     ascending j (x = the bf16 gradient as float);
+//   * the n % 8 tail elements go to the accumulators of groups 0..n%8-1,
+//     after the group's own sum;
+//   * 64 consecutive groups through the __shfl_down tree (one wave of the
+//     norm kernel = one 512-element block here);
+//   * four consecutive tree sums added in order from 0 (one 2048-element
+//     block of the norm kernel);
+//   * those sums lane-strided by 64 from 0, then the same tree.
+// One element per thread as in slab_reduce_pair_kernel (the 64-image sum is
+// where the traffic is), 512 threads so that a block holds one whole tree:
+// wave 0 forms the 64 group sums from the block's bf16 results (LDS) and
+// stores the tree sum at sqnorm[1 + block], write-through. Thread 0 then
+// bumps the chain's integer counter; the block that draws the last ticket adds
+// the tree sums up in the fixed order, stores sqnorm[0] and resets the
+// counter for the next launch. No block waits for another, and no float
+// atomic enters the sum. Block 0 recomputes the (at most 7) tail elements
+// from the slab, the same ascending sum, so it needs nothing from the
+// block that owns them.
+struct TailChain {
+  const float* slab;  // [WG_SLICES, slab_stride]
+  __bf16* grad16;     // [n]
+  long slab_stride, n;
+  float* sqnorm;      // [0] = total, [1 + b] = tree sum of block b
+  long* step_t;
+  unsigned int* counter;  // zero between launches
+};
+
+__device__ __forceinline__ float slab_sum(const float* __restrict__ slab,
+                                          long slab_stride, long i) {
+  // all 64 loads go out before the first add; the adds keep their order
+  float v[WG_SLICES];
+#pragma unroll
+  for (int z = 0; z < WG_SLICES; ++z) v[z] = slab[(long)z * slab_stride + i];
+  float s = 0.0f;
+#pragma unroll
+  for (int z = 0; z < WG_SLICES; ++z) s += v[z];
+  return s;
+}
+
+extern "C" __launch_bounds__(512) __global__
+    void slab_reduce_norm_pair_kernel(TailChain c0, TailChain c1) {
+  const TailChain c = blockIdx.y ? c1 : c0;
+  const long n = c.n;
+  const int nblk = (int)((n + 511) / 512);
+  if ((int)blockIdx.x >= nblk) return;  // the shorter chain's spare blocks
+  if (blockIdx.x == 0 && threadIdx.x == 0) *c.step_t += 1;
+  __shared__ float x[512];
+  __shared__ int is_last;
+  const long i = (long)blockIdx.x * 512 + threadIdx.x;
+  float xv = 0.0f;
+  if (i < n) {
+    const __bf16 q = (__bf16)slab_sum(c.slab, c.slab_stride, i);
+    c.grad16[i] = q;
+    xv = (float)q;
+  }
+  x[threadIdx.x] = xv;
+  __syncthreads();
+  const long nvec = n / 8;
+  if (threadIdx.x < 64) {
+    float acc = 0.0f;
+    if ((long)blockIdx.x * 64 + threadIdx.x < nvec) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = x[threadIdx.x * 8 + j];
+        acc += v * v;
+      }
+    }
+    if (blockIdx.x == 0 && (long)threadIdx.x < n - nvec * 8) {
+      float v = (float)(__bf16)slab_sum(c.slab, c.slab_stride,
+                                        nvec * 8 + threadIdx.x);
+      acc += v * v;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    if (threadIdx.x == 0) {
+      // publish the one float write-through and wait for it, then take a
+      // ticket. A release fence here would write the whole L2 back, the
+      // block's share of grad16 included, once per block (measured: 22 us
+      // for the launch against 9 us for the plain reduce).
+      __hip_atomic_store(c.sqnorm + 1 + blockIdx.x, acc, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      is_last = __hip_atomic_fetch_add(c.counter, 1u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT) ==
+                (unsigned int)(nblk - 1);
+    }
+  }
+  __syncthreads();
+  if (!is_last || threadIdx.x >= 64) return;
+  // every block sum was acknowledged before its ticket; read them past
+  // this CU's cache (agent-scope loads)
+  // the norm kernel's blocks: 256 groups each, at least one
+  const long nb = nvec > 256 ? (nvec + 255) / 256 : 1;
+  float acc = 0.0f;
+  for (long p = threadIdx.x; p < nb; p += 64) {
+    float s = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const long b = 4 * p + w;
+      // a tree the norm kernel would run over no data is a zero
+      s += b < nblk ? __hip_atomic_load(c.sqnorm + 1 + b, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT)
+                    : 0.0f;
+    }
+    acc += s;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  if (threadIdx.x == 0) {
+    c.sqnorm[0] = acc;
+    __hip_atomic_store(c.counter, 0u, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// n0, n1 >= 1; each sqnorm holds 1 + ceil(n / 512) floats (bind.cpp checks)
+extern "C" void launch_slab_reduce_norm_pair(
+    const float* slab0, void* grad0, long stride0, long n0, float* sqnorm0,
+    long* step0, unsigned int* counter0, const float* slab1, void* grad1,
+    long stride1, long n1, float* sqnorm1, long* step1,
+    unsigned int* counter1, void* stream) {
+  TailChain c0{slab0, (__bf16*)grad0, stride0, n0, sqnorm0, step0, counter0};
+  TailChain c1{slab1, (__bf16*)grad1, stride1, n1, sqnorm1, step1, counter1};
+  long nmax = n0 > n1 ? n0 : n1;
+  int blocks = (int)((nmax + 511) / 512);
+  hipLaunchKernelGGL(slab_reduce_norm_pair_kernel, dim3(blocks, 2), dim3(512),
+                     0, (hipStream_t)stream, c0, c1);
+}
+
 // ------------------------------------------------------------- tr probe
 // Empirically maps __builtin_amdgcn_ds_read_tr16_b64_v4bf16: stages 1024
 // known bf16 values linearly in LDS, issues the tr read with per-lane base

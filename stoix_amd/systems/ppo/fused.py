@@ -12,8 +12,9 @@ stoix_amd/ops/csrc/mlp.hip:
                  physics + autoreset + bootstrap critic, ONE launch); or
                  policy_value_step -> env HIP step -> value_forward for
                  non-Ant HIP envs
-  minibatch:     ppo_gather -> layer-1 fused linear_silu per net (custom
-                 MFMA wins at K=32) -> layer-2 tuned hipBLASLt GemmAndBias
+  minibatch:     ppo_gather -> layer-1 fused linear_silu_pair, both nets in
+                 one launch over the shared Xmb (custom MFMA wins at K=32,
+                 row-contiguous stores) -> layer-2 tuned hipBLASLt GemmAndBias
                  per net (library wins at K=256) -> silu_heads_fwd (ONE
                  stacked silu that also forms both heads from the tile it
                  holds) -> ppo_head_loss (per-row losses + analytic
@@ -22,13 +23,15 @@ stoix_amd/ops/csrc/mlp.hip:
                  (head dgrads formed inside the layer-2 silu backward),
                  one silu_bwd for layer 1, dH1 as one batched bmm against the
                  adjacent-W2 [2, H, H] view, split-K wgrads into per-chain
-                 slabs (wgrad_pair: both nets per launch) -> one
-                 slab_reduce_pair over both chains
-                 -> ONE bf16 RCCL all-reduce over both chains' shared
-                 grad buffer
-                 -> fused_adam_bf16 per chain (clip + Adam + bf16 mirror;
-                 per-chain lr and global-norm clip match the reference's
-                 per-network optax chains)
+                 slabs (wgrad_pair: both nets per launch)
+                 -> one GPU: slab_reduce_norm_pair (both chains' reduce +
+                 squared norms) -> adam_pair (both chains' clip + Adam +
+                 bf16 mirror), two launches
+                 -> several GPUs: slab_reduce_pair -> ONE bf16 RCCL
+                 all-reduce over both chains' shared grad buffer ->
+                 fused_adam_bf16 per chain
+                 (per-chain lr and global-norm clip match the reference's
+                 per-network optax chains either way)
 
 Parameters: fp32 masters live in ONE flat buffer per network (the module
 parameters are repointed to views, so evaluator/checkpointing see updates
@@ -117,7 +120,13 @@ class _Chain:
         # [0] = squared grad norm; [1:] = room for one partial sum per block
         # of the norm kernel (<= 2048 blocks), which fused_adam_bf16 then
         # adds in a fixed order: bit-reproducible clipping run to run
-        self.sqnorm = torch.zeros(1 + 2048, dtype=torch.float32, device=device)
+        # The two-launch tail (slab_reduce_norm_pair) keeps one sum per 512
+        # elements there instead, so the range grows with the chain; its
+        # arrival counter is a word of its own, zero between launches.
+        self.sqnorm = torch.zeros(
+            1 + max(2048, (total + 511) // 512), dtype=torch.float32, device=device
+        )
+        self.tail_counter = torch.zeros(1, dtype=torch.int32, device=device)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=device)
         self.views: Dict[str, Tensor] = {}
         self.views16: Dict[str, Tensor] = {}
@@ -373,6 +382,15 @@ class FusedPPOEngine:
         # the slabs un-zeroed; 0 = six wgrad launches + two zeroing reduces.
         # Same gradients bit for bit (wgrad.hip keeps the summation order).
         self.fused_wgrad = _os.environ.get("STOIX_FUSED_WGRAD", "1") != "0"
+        # STOIX_FUSED_L1: 1 (default) = both nets' layer-1 Linear+SiLU in
+        # one launch with row-contiguous stores (linear_silu_pair); 0 = one
+        # linear_silu per net. Same Z1/H1 bit for bit.
+        self.fused_l1 = _os.environ.get("STOIX_FUSED_L1", "1") != "0"
+        # STOIX_FUSED_TAIL: 1 (default) = the optimiser tail as two launches
+        # (slab_reduce_norm_pair -> adam_pair); 0 = slab reduce, then norm +
+        # Adam per chain (five launches). Same norm, same updates bit for
+        # bit. Where the two-launch form applies: _tail_eligible.
+        self.fused_tail = _os.environ.get("STOIX_FUSED_TAIL", "1") != "0"
         self.no_vpred = z(0)
         # side-stream gather prefetch. Measured SLOWER (28.0 vs 26.8
         # ms/step): the backward kernels already fill all 256 CUs, so the
@@ -402,6 +420,33 @@ class FusedPPOEngine:
         # the rollout reads the env's stable obs buffer directly; seed it
         # with the current observation (reset happened before attach)
         learner.env._hb["obs"].copy_(learner.cur_obs)
+
+    def _tail_eligible(self) -> bool:
+        """The two-launch optimiser tail needs the paired slab reduce, no
+        all-reduce between reduce and norm, a clip (the norm is computed
+        either way), and chains short enough for the ordered norm of
+        fused_adam_bf16 to be one vector per thread."""
+        cap = int(self.ext.TAIL_MAX_N)
+        return (
+            self.fused_tail and self.fused_wgrad and self.world == 1
+            and self.max_grad_norm > 0.0
+            and self.actor_chain.numel <= cap and self.critic_chain.numel <= cap
+        )
+
+    def layer1_forward(self, Xmb: Tensor) -> None:
+        """Z1/H1 of both nets from one minibatch input: the paired kernel
+        where it takes the shape, else (or with the knob off) one
+        linear_silu per net."""
+        ext = self.ext
+        ac, cc = self.actor_chain, self.critic_chain
+        a16, c16 = ac.views16, cc.views16
+        if self.fused_l1 and ext.linear_silu_pair(
+            Xmb, a16["W1"], ac.views["b1"], self.Z1[0], self.H1[0],
+            c16["W1"], cc.views["b1"], self.Z1[1], self.H1[1],
+        ):
+            return
+        ext.linear_silu(Xmb, a16["W1"], ac.views["b1"], self.Z1[0], self.H1[0], 1)
+        ext.linear_silu(Xmb, c16["W1"], cc.views["b1"], self.Z1[1], self.H1[1], 1)
 
     # ------------------------------------------------------------- params
 
@@ -619,6 +664,7 @@ class FusedPPOEngine:
                 gather_into(0, self.ws[0])
                 self.ev_ready[0].record(gs)
 
+        tail = self._tail_eligible()
         for mb in range(n_mb):
             p = mb & 1 if prefetch else 0
             w = self.ws[p]
@@ -631,8 +677,7 @@ class FusedPPOEngine:
             # (K=256): hipBLASLt's tuned GemmAndBias (14.4 us) beats the
             # custom kernel (24.6 us), so run both nets' GEMMs then ONE
             # silu over the stacked [2, S, H] preacts.
-            ext.linear_silu(w.Xmb, a16["W1"], ac.views["b1"], self.Z1[0], self.H1[0], 1)
-            ext.linear_silu(w.Xmb, c16["W1"], cc.views["b1"], self.Z1[1], self.H1[1], 1)
+            self.layer1_forward(w.Xmb)
             torch.addmm(a16["b2"], self.H1[0], a16["W2"].t(), out=self.Z2[0])
             torch.addmm(c16["b2"], self.H1[1], c16["W2"].t(), out=self.Z2[1])
             # ---- silu + the actor head in one pass over Z2 (the N=16 head
@@ -730,6 +775,19 @@ class FusedPPOEngine:
                     with torch.cuda.stream(gs):
                         gather_into(mb + 1, self.ws[q])
                         self.ev_ready[q].record(gs)
+            if tail:
+                # reduce + both norms, then both Adams: two launches
+                ext.slab_reduce_norm_pair(
+                    ac.slab, ac.grad16, ac.sqnorm, ac.step_t, ac.tail_counter,
+                    cc.slab, cc.grad16, cc.sqnorm, cc.step_t, cc.tail_counter)
+                ext.adam_pair(
+                    ac.flat, ac.grad16, ac.m, ac.v, ac.sqnorm, ac.step_t,
+                    ac.flat16, ac.lr,
+                    cc.flat, cc.grad16, cc.m, cc.v, cc.sqnorm, cc.step_t,
+                    cc.flat16, cc.lr,
+                    0.9, 0.999, 1e-5, self.max_grad_norm, 1.0,
+                )
+                continue
             if pair:
                 # no zeroing pass: the wgrads store (never accumulate), so
                 # the next minibatch overwrites every element summed here
