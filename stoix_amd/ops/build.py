@@ -7,6 +7,7 @@ would not). hipcc cross-compiles gfx950 without a GPU present.
 """
 from __future__ import annotations
 
+import hashlib
 import os
 from pathlib import Path
 
@@ -29,6 +30,17 @@ SOURCES = [
 ]
 
 
+def _headers_digest() -> str:
+    """Digest of csrc/*.h for the hipcc command line. ninja gets a depfile
+    from the host compiler only (bind.cpp); the hipcc rule writes none, so an
+    edited header would leave every .hip object stale. ninja does compare
+    command lines, so a define that carries the digest rebuilds them."""
+    h = hashlib.sha1()
+    for p in sorted(CSRC.glob("*.h")):
+        h.update(p.read_bytes())
+    return h.hexdigest()[:16]
+
+
 def build(verbose: bool = False):
     """Compile (if stale) and return the loaded module."""
     os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
@@ -41,7 +53,8 @@ def build(verbose: bool = False):
         name="stoix_amd_C",
         sources=sources,
         extra_cflags=["-O3", "-std=c++17"],
-        extra_cuda_cflags=["-O3", "-std=c++17", "--offload-arch=gfx950"],
+        extra_cuda_cflags=["-O3", "-std=c++17", "--offload-arch=gfx950",
+                           f"-DSTOIX_CSRC_HEADERS=0x{_headers_digest()}"],
         build_directory=str(BUILD_DIR),
         verbose=verbose,
         with_cuda=True,

@@ -2,162 +2,13 @@
 //
 // Pure-C++ translation layer: validates torch tensors, extracts raw
 // pointers + the current HIP stream, and calls the extern "C" launchers
-// defined in the .hip files. Every entry point takes the stream from
-// PyTorch's current stream so the kernels compose with torch ops and with
-// hip graph capture.
+// that launchers.h declares and the .hip files define. Every entry point
+// takes the stream from PyTorch's current stream so the kernels compose with
+// torch ops and with hip graph capture.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include <cstdint>
-
-extern "C" {
-void launch_cartpole_step(float*, const long*, int*, float*, int*, float*,
-                          int*, float*, float*, float*, float*, unsigned char*,
-                          unsigned char*, int, int, uint64_t, unsigned int*,
-                          unsigned int, int, void*);
-void launch_ant_step(float*, const float*, int*, float*, int*, float*, int*,
-                     float*, float*, float*, float*, unsigned char*,
-                     unsigned char*, int, int, uint64_t, unsigned int*,
-                     unsigned int, int, void*);
-void launch_humanoid_step(float*, const float*, int*, float*, int*, float*,
-                          int*, float*, float*, float*, float*,
-                          unsigned char*, unsigned char*, int, int, uint64_t,
-                          unsigned int*, unsigned int, int, void*);
-void launch_ant_reset(float*, int, uint64_t, uint32_t, void*);
-void launch_gae(const float*, const float*, const float*, const float*,
-                const unsigned char*, float*, float*, int, int, float, void*);
-void launch_lambda_returns(const float*, const float*, const float*, float*,
-                           int, int, float, void*);
-void launch_vtrace(const float*, const float*, const float*, const float*,
-                   const float*, float*, float*, int, int, float, float,
-                   float, void*);
-void launch_offpolicy_returns(const float*, const float*, const float*,
-                              const float*, const float*, float*, int, int,
-                              void*);
-void launch_fused_adam(float*, const float*, float*, float*, float*, long*,
-                       long, float, float, float, float, float, void*);
-void launch_fused_adam_bf16(float*, const void*, float*, float*, float*,
-                            long*, void*, long, float, float, float, float,
-                            float, float, int, long, void*);
-void launch_polyak(const float*, float*, long, float, void*);
-void launch_mfma_probe(const void*, const void*, float*, float*, void*);
-void launch_policy_value_step(const float*, const void*, const float*,
-                              const void*, const float*, const void*,
-                              const float*, const void*, const float*,
-                              const void*, const float*, const void*,
-                              const float*, float*, float*, float*, float*,
-                              const float*, const float*, int, int, int, int,
-                              float, float, float, float, int, uint64_t,
-                              unsigned int*, unsigned int, int, void*);
-void launch_value_forward(const float*, const void*, const float*,
-                          const void*, const float*, const void*,
-                          const float*, float*, const float*, const float*,
-                          int, int, int, void*);
-void launch_rollout_step_ant(float*, float*, int*, float*, int*, float*,
-                             int*, const void*, const float*, const void*,
-                             const float*, const void*, const float*,
-                             const void*, const float*, const void*,
-                             const float*, const void*, const float*, float*,
-                             float*, float*, float*, float*, float*, float*,
-                             unsigned char*, int, int, int, int, int, float,
-                             float, float, float, uint64_t, uint64_t,
-                             unsigned int*, unsigned int*, unsigned int,
-                             void*);
-void launch_linear_silu(const void*, const void*, const float*, void*,
-                        void*, int, int, int, int, void*);
-void launch_silu_fwd(const void*, void*, long, void*);
-void launch_silu_bwd(const void*, const void*, void*, long, void*);
-void launch_silu_heads_fwd(const void*, const void*, const void*, const void*,
-                           const void*, void*, void*, void*, int, int, void*);
-void launch_heads_bwd_silu(const void*, const void*, const void*, const void*,
-                           const void*, void*, int, int, void*);
-void launch_ppo_gather(const long*, int, const float*, int, int,
-                       const float*, int,
-                       const float*, const float*, const float*, const float*,
-                       void*, float*, float*, float*, float*, float*,
-                       const float*, const float*, void*);
-void launch_ppo_head_loss(const void*, const void*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, void*, void*, void*, float*, int,
-                          int, float, float, float, float, float, float,
-                          float, uint64_t, unsigned int*, unsigned int, int,
-                          void*);
-void launch_wgrad(const void*, const void*, float*, long, long, long, int,
-                  int, int, int, int, int, void*);
-void launch_slab_reduce(float*, void*, long, long, float*, long*, void*);
-void launch_bump_add(unsigned int*, unsigned int, void*);
-void launch_tr16_probe(const void*, float*, int, void*);
-int launch_wgrad_pair(const void*, const void*, float*, long, long, long, int,
-                      const void*, const void*, float*, long, long, long, int,
-                      int, int, int, int, void*);
-void launch_slab_reduce_pair(const float*, void*, long, long, float*, long*,
-                             const float*, void*, long, long, float*, long*,
-                             void*);
-int launch_linear_silu_pair(const void*, const void*, const float*, void*,
-                            void*, const void*, const float*, void*, void*,
-                            int, int, int, void*);
-void launch_slab_reduce_norm_pair(const float*, void*, long, long, float*,
-                                  long*, unsigned int*, const float*, void*,
-                                  long, long, float*, long*, unsigned int*,
-                                  void*);
-void launch_adam_pair(float*, const void*, float*, float*, const float*,
-                      const long*, void*, long, float, float*, const void*,
-                      float*, float*, const float*, const long*, void*, long,
-                      float, float, float, float, float, float, void*);
-void launch_sumtree_update(float*, const long*, const float*, long, int, int,
-                           void*);
-void launch_sumtree_sample(const float*, const float*, long*, long, int, int,
-                           int, void*);
-void launch_policy_value_step_disc(const float*, const void*, const float*,
-                                   const void*, const float*, const void*,
-                                   const float*, const void*, const float*,
-                                   const void*, const float*, const void*,
-                                   const float*, float*, long*, float*,
-                                   float*, const float*, const float*, int,
-                                   int, int, int, int, uint64_t,
-                                   unsigned int*, unsigned int, int, void*);
-void launch_ppo_head_loss_disc(const void*, const void*, const long*,
-                               const float*, const float*, const float*,
-                               const float*, void*, void*, void*, float*,
-                               int, int, float, float, float, void*);
-void launch_ppo_gather_disc(const long*, int, const float*, int, int,
-                            const long*, const float*, const float*,
-                            const float*, const float*, void*, long*, float*,
-                            float*, float*, float*, const float*,
-                            const float*, void*);
-void launch_rnn_scan(const float*, const void*, const float*,
-                     const unsigned char*, const float*, const float*,
-                     float*, float*, float*, int, int, int, int, void*);
-void launch_rnn_scan_train_fwd(const float*, const void*, const float*,
-                               const unsigned char*, const float*,
-                               const float*, float*, float*, float*, float*,
-                               float*, int, int, int, int, void*);
-void launch_rnn_scan_bwd(const float*, const float*, const float*,
-                         const float*, const float*, const float*,
-                         const float*, const float*, const unsigned char*,
-                         const void*, float*, float*, float*, float*, int,
-                         int, int, int, void*);
-void launch_snake_step(int*, long*, long*, long*, long*, int*, const long*,
-                       int*, float*, int*, float*, int*, float*, float*,
-                       float*, float*, unsigned char*, unsigned char*, int,
-                       int, uint64_t, unsigned int*, unsigned int, int,
-                       void*);
-void launch_c51_loss_fwd(const void*, const float*, const long*, const float*,
-                         const float*, const void*, const float*,
-                         const float*, float*, float*, float*, int, int, int,
-                         int, int, int, long, long, long, void*);
-void launch_c51_loss_bwd(const float*, long, const void*, const long*,
-                         const float*, const float*, void*, int, int, int,
-                         int, long, void*);
-void launch_mcts_select(const float*, const float*, const float*, const float*,
-                        const float*, const long*, const float*, const float*,
-                        long*, long*, int, int, int, float, void*);
-void launch_mcts_expand_backup(float*, float*, float*, float*, float*, long*,
-                               long*, long*, float*, float*, const long*,
-                               const long*, const float*, const float*,
-                               const float*, const float*, int, int, int, int,
-                               void*);
-}
+#include "launchers.h"
 
 namespace {
 
@@ -170,31 +21,26 @@ void* cur_stream() {
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous");          \
   TORCH_CHECK((t).scalar_type() == ty, #t " has wrong dtype");
 
-void cartpole_step(torch::Tensor state, torch::Tensor action,
-                   torch::Tensor step_count, torch::Tensor ep_return,
-                   torch::Tensor ep_length, torch::Tensor last_ep_return,
-                   torch::Tensor last_ep_length, torch::Tensor obs_out,
-                   torch::Tensor next_obs_out, torch::Tensor reward_out,
-                   torch::Tensor discount_out, torch::Tensor steptype_out,
-                   torch::Tensor done_out, int64_t max_episode_steps,
-                   int64_t seed, torch::Tensor draw_buf, int64_t draw_offset,
-                   int64_t do_bump) {
-  CHK(state, torch::kFloat32);
-  CHK(action, torch::kInt64);
-  int B = state.size(0);
-  launch_cartpole_step(
-      state.data_ptr<float>(), action.data_ptr<long>(),
-      step_count.data_ptr<int>(), ep_return.data_ptr<float>(),
-      ep_length.data_ptr<int>(), last_ep_return.data_ptr<float>(),
-      last_ep_length.data_ptr<int>(), obs_out.data_ptr<float>(),
-      next_obs_out.data_ptr<float>(), reward_out.data_ptr<float>(),
-      discount_out.data_ptr<float>(), steptype_out.data_ptr<unsigned char>(),
-      done_out.data_ptr<unsigned char>(), B, (int)max_episode_steps,
-      (uint64_t)seed, (unsigned int*)draw_buf.data_ptr<int>(),
-      (unsigned int)draw_offset, (int)do_bump, cur_stream());
+// Optional operands: a tensor with no elements stands for a null pointer.
+template <typename T>
+T* ptr_or_null(const torch::Tensor& t) {
+  return t.numel() > 0 ? t.data_ptr<T>() : nullptr;
 }
 
-void ant_step(torch::Tensor state, torch::Tensor action,
+float* fptr_or_null(const torch::Tensor& t) { return ptr_or_null<float>(t); }
+
+void* vptr_or_null(const torch::Tensor& t) {
+  return t.numel() > 0 ? t.data_ptr() : nullptr;
+}
+
+unsigned int* draw_or_null(const torch::Tensor& draw_buf) {
+  return (unsigned int*)ptr_or_null<int>(draw_buf);
+}
+
+// cartpole_step, ant_step and humanoid_step: one wrapper, the action type
+// and the launcher differ.
+template <typename Action, auto Launch>
+void env_step(torch::Tensor state, torch::Tensor action,
               torch::Tensor step_count, torch::Tensor ep_return,
               torch::Tensor ep_length, torch::Tensor last_ep_return,
               torch::Tensor last_ep_length, torch::Tensor obs_out,
@@ -203,34 +49,10 @@ void ant_step(torch::Tensor state, torch::Tensor action,
               torch::Tensor done_out, int64_t max_episode_steps, int64_t seed,
               torch::Tensor draw_buf, int64_t draw_offset, int64_t do_bump) {
   CHK(state, torch::kFloat32);
-  CHK(action, torch::kFloat32);
+  CHK(action, c10::CppTypeToScalarType<Action>::value);
   int B = state.size(0);
-  launch_ant_step(
-      state.data_ptr<float>(), action.data_ptr<float>(),
-      step_count.data_ptr<int>(), ep_return.data_ptr<float>(),
-      ep_length.data_ptr<int>(), last_ep_return.data_ptr<float>(),
-      last_ep_length.data_ptr<int>(), obs_out.data_ptr<float>(),
-      next_obs_out.data_ptr<float>(), reward_out.data_ptr<float>(),
-      discount_out.data_ptr<float>(), steptype_out.data_ptr<unsigned char>(),
-      done_out.data_ptr<unsigned char>(), B, (int)max_episode_steps,
-      (uint64_t)seed, (unsigned int*)draw_buf.data_ptr<int>(),
-      (unsigned int)draw_offset, (int)do_bump, cur_stream());
-}
-
-void humanoid_step(torch::Tensor state, torch::Tensor action,
-                   torch::Tensor step_count, torch::Tensor ep_return,
-                   torch::Tensor ep_length, torch::Tensor last_ep_return,
-                   torch::Tensor last_ep_length, torch::Tensor obs_out,
-                   torch::Tensor next_obs_out, torch::Tensor reward_out,
-                   torch::Tensor discount_out, torch::Tensor steptype_out,
-                   torch::Tensor done_out, int64_t max_episode_steps,
-                   int64_t seed, torch::Tensor draw_buf, int64_t draw_offset,
-                   int64_t do_bump) {
-  CHK(state, torch::kFloat32);
-  CHK(action, torch::kFloat32);
-  int B = state.size(0);
-  launch_humanoid_step(
-      state.data_ptr<float>(), action.data_ptr<float>(),
+  Launch(
+      state.data_ptr<float>(), action.data_ptr<Action>(),
       step_count.data_ptr<int>(), ep_return.data_ptr<float>(),
       ep_length.data_ptr<int>(), last_ep_return.data_ptr<float>(),
       last_ep_length.data_ptr<int>(), obs_out.data_ptr<float>(),
@@ -280,10 +102,9 @@ void gae(torch::Tensor r_t, torch::Tensor discount_t, torch::Tensor v_tm1,
   if (trunc_t.numel() > 0)
     scan_operand_check(trunc_t, r_t, "trunc_t", torch::kUInt8);
   int T = r_t.size(0), B = r_t.size(1);
-  const unsigned char* tr =
-      trunc_t.numel() > 0 ? trunc_t.data_ptr<unsigned char>() : nullptr;
   launch_gae(r_t.data_ptr<float>(), discount_t.data_ptr<float>(),
-             v_tm1.data_ptr<float>(), v_t.data_ptr<float>(), tr,
+             v_tm1.data_ptr<float>(), v_t.data_ptr<float>(),
+             ptr_or_null<unsigned char>(trunc_t),
              adv_out.data_ptr<float>(), target_out.data_ptr<float>(), T, B,
              (float)lambda_, cur_stream());
 }
@@ -361,12 +182,12 @@ void fused_adam_bf16(torch::Tensor param, torch::Tensor grad,
                      double grad_scale, int64_t do_prologue) {
   CHK(param, torch::kFloat32);
   CHK(grad, torch::kBFloat16);
-  void* pbf = param_bf16.numel() > 0 ? param_bf16.data_ptr() : nullptr;
   launch_fused_adam_bf16(param.data_ptr<float>(), grad.data_ptr(),
                          exp_avg.data_ptr<float>(),
                          exp_avg_sq.data_ptr<float>(),
                          sqnorm.data_ptr<float>(), step_t.data_ptr<long>(),
-                         pbf, param.numel(), (float)lr, (float)beta1,
+                         vptr_or_null(param_bf16), param.numel(), (float)lr,
+                         (float)beta1,
                          (float)beta2, (float)eps, (float)max_norm,
                          (float)grad_scale, (int)do_prologue,
                          (long)sqnorm.numel(), cur_stream());
@@ -377,15 +198,6 @@ void mfma_probe(torch::Tensor A, torch::Tensor B, torch::Tensor D0,
   CHK(A, torch::kBFloat16);
   launch_mfma_probe(A.data_ptr(), B.data_ptr(), D0.data_ptr<float>(),
                     D1.data_ptr<float>(), cur_stream());
-}
-
-const float* fptr_or_null(const torch::Tensor& t) {
-  return t.numel() > 0 ? t.data_ptr<float>() : nullptr;
-}
-
-unsigned int* draw_or_null(const torch::Tensor& draw_buf) {
-  return draw_buf.numel() > 0 ? (unsigned int*)draw_buf.data_ptr<int>()
-                              : nullptr;
 }
 
 // A fused-MLP weight (mlp.hip): contiguous bf16 on the GPU, `rows` x `cols`.
@@ -444,16 +256,15 @@ void policy_value_step(torch::Tensor obs, torch::Tensor W1a, torch::Tensor b1a,
   int B = obs.size(0), OBS = obs.size(1);
   int ACT = action_out.size(1);
   int HID = check_fused_mlp(obs, W1a, W2a, Wha, W1c, W2c, Wvc, ACT, 8);
-  float* om = obs_mirror.numel() > 0 ? obs_mirror.data_ptr<float>() : nullptr;
   launch_policy_value_step(
       obs.data_ptr<float>(), W1a.data_ptr(), b1a.data_ptr<float>(),
       W2a.data_ptr(), b2a.data_ptr<float>(), Wha.data_ptr(),
       bha.data_ptr<float>(), W1c.data_ptr(), b1c.data_ptr<float>(),
       W2c.data_ptr(), b2c.data_ptr<float>(), Wvc.data_ptr(),
-      bvc.data_ptr<float>(), om, action_out.data_ptr<float>(),
-      logp_out.data_ptr<float>(), value_out.data_ptr<float>(),
-      fptr_or_null(nmean), fptr_or_null(nvar), B, OBS, ACT, HID,
-      (float)min_scale, (float)aff_scale, (float)aff_shift,
+      bvc.data_ptr<float>(), fptr_or_null(obs_mirror),
+      action_out.data_ptr<float>(), logp_out.data_ptr<float>(),
+      value_out.data_ptr<float>(), fptr_or_null(nmean), fptr_or_null(nvar), B,
+      OBS, ACT, HID, (float)min_scale, (float)aff_scale, (float)aff_shift,
       (float)log_aff_scale, (int)greedy, (uint64_t)seed,
       draw_or_null(draw_buf), (unsigned int)draw_offset, (int)do_bump,
       cur_stream());
@@ -472,15 +283,15 @@ void policy_value_step_disc(
   int B = obs.size(0), OBS = obs.size(1);
   int ACT = (int)num_actions;
   int HID = check_fused_mlp(obs, W1a, W2a, Wha, W1c, W2c, Wvc, ACT, 16);
-  float* om = obs_mirror.numel() > 0 ? obs_mirror.data_ptr<float>() : nullptr;
   launch_policy_value_step_disc(
       obs.data_ptr<float>(), W1a.data_ptr(), b1a.data_ptr<float>(),
       W2a.data_ptr(), b2a.data_ptr<float>(), Wha.data_ptr(),
       bha.data_ptr<float>(), W1c.data_ptr(), b1c.data_ptr<float>(),
       W2c.data_ptr(), b2c.data_ptr<float>(), Wvc.data_ptr(),
-      bvc.data_ptr<float>(), om, action_out.data_ptr<long>(),
-      logp_out.data_ptr<float>(), value_out.data_ptr<float>(),
-      fptr_or_null(nmean), fptr_or_null(nvar), B, OBS, ACT, HID, (int)greedy,
+      bvc.data_ptr<float>(), fptr_or_null(obs_mirror),
+      action_out.data_ptr<long>(), logp_out.data_ptr<float>(),
+      value_out.data_ptr<float>(), fptr_or_null(nmean), fptr_or_null(nvar), B,
+      OBS, ACT, HID, (int)greedy,
       (uint64_t)seed, draw_or_null(draw_buf), (unsigned int)draw_offset,
       (int)do_bump, cur_stream());
 }
@@ -499,8 +310,7 @@ void ppo_head_loss_disc(torch::Tensor heads, torch::Tensor v_in,
       heads.data_ptr(), v_in.data_ptr(), action.data_ptr<long>(),
       old_logp.data_ptr<float>(), old_value.data_ptr<float>(),
       adv.data_ptr<float>(), targets.data_ptr<float>(), dhead.data_ptr(),
-      dv.data_ptr(), dv16.numel() > 0 ? dv16.data_ptr() : nullptr,
-      metrics.numel() > 0 ? metrics.data_ptr<float>() : nullptr, B,
+      dv.data_ptr(), vptr_or_null(dv16), fptr_or_null(metrics), B,
       (int)num_actions, (float)clip_eps, (float)ent_coef, (float)vf_coef,
       cur_stream());
 }
@@ -596,9 +406,9 @@ void linear_silu(torch::Tensor X, torch::Tensor W, torch::Tensor bias,
   int S = X.size(0), K = X.size(1), N = W.size(0);
   TORCH_CHECK(S % 128 == 0 && N % 128 == 0 && K % 32 == 0,
               "linear_silu tile constraints");
-  void* h = H.numel() > 0 ? H.data_ptr() : nullptr;
   launch_linear_silu(X.data_ptr(), W.data_ptr(), bias.data_ptr<float>(),
-                     Z.data_ptr(), h, S, K, N, (int)do_silu, cur_stream());
+                     Z.data_ptr(), vptr_or_null(H), S, K, N, (int)do_silu,
+                     cur_stream());
 }
 
 // Both nets' layer-1 Linear+SiLU in one launch over a shared X. Returns
@@ -632,11 +442,12 @@ bool linear_silu_pair(torch::Tensor X, torch::Tensor W_a, torch::Tensor b_a,
   for (const torch::Tensor* t : {&X, &W_a, &W_c, &Z_a, &H_a, &Z_c, &H_c})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
                 "linear_silu_pair: operands must be 16-byte aligned");
-  return launch_linear_silu_pair(
-             X.data_ptr(), W_a.data_ptr(), b_a.data_ptr<float>(),
-             Z_a.data_ptr(), H_a.data_ptr(), W_c.data_ptr(),
-             b_c.data_ptr<float>(), Z_c.data_ptr(), H_c.data_ptr(), (int)S,
-             (int)K, (int)N, cur_stream()) == 0;
+  const LinSiluNet na{W_a.data_ptr(), b_a.data_ptr<float>(), Z_a.data_ptr(),
+                      H_a.data_ptr()};
+  const LinSiluNet nc{W_c.data_ptr(), b_c.data_ptr<float>(), Z_c.data_ptr(),
+                      H_c.data_ptr()};
+  return launch_linear_silu_pair(X.data_ptr(), na, nc, (int)S, (int)K, (int)N,
+                                 cur_stream()) == 0;
 }
 
 void silu_fwd(torch::Tensor z, torch::Tensor h) {
@@ -693,7 +504,7 @@ void silu_heads_fwd(torch::Tensor Z2, torch::Tensor Wh, torch::Tensor bh,
   launch_silu_heads_fwd(Z2.data_ptr(), Wh.data_ptr(), bh.data_ptr(),
                         Wv.data_ptr(), bv.data_ptr(), H2.data_ptr(),
                         heads.data_ptr(),
-                        vpred.numel() > 0 ? vpred.data_ptr() : nullptr, S,
+                        vptr_or_null(vpred), S,
                         HID, cur_stream());
 }
 
@@ -743,91 +554,126 @@ void ppo_head_loss(torch::Tensor heads, torch::Tensor v_in,
   CHK(action, torch::kFloat32);
   int B = heads.size(0), ACT = action.size(1);
   TORCH_CHECK(heads.size(1) == 16, "heads must be [B,16] (loc|scale packed)");
-  void* dv16p = dv16.numel() > 0 ? dv16.data_ptr() : nullptr;
-  float* mp = metrics.numel() > 0 ? metrics.data_ptr<float>() : nullptr;
   launch_ppo_head_loss(
       heads.data_ptr(), v_in.data_ptr(), action.data_ptr<float>(),
       old_logp.data_ptr<float>(), old_value.data_ptr<float>(),
       adv.data_ptr<float>(), targets.data_ptr<float>(), dhead.data_ptr(),
-      dv.data_ptr(), dv16p, mp, B, ACT,
-      (float)clip_eps,
-      (float)ent_coef, (float)vf_coef, (float)min_scale, (float)aff_scale,
-      (float)aff_shift, (float)log_aff_scale, (uint64_t)seed,
+      dv.data_ptr(), vptr_or_null(dv16), fptr_or_null(metrics), B, ACT,
+      (float)clip_eps, (float)ent_coef, (float)vf_coef, (float)min_scale,
+      (float)aff_scale, (float)aff_shift, (float)log_aff_scale, (uint64_t)seed,
       draw_or_null(draw_buf), (unsigned int)draw_offset, (int)do_bump,
       cur_stream());
+}
+
+// One net's operands for wgrad() / wgrad_pair() (wgrad.hip): dZ [S, N_STRIDE]
+// and X [S, K] in bf16, and the dW [n_valid, K] and db [n_valid] ranges
+// inside one image of the [>= 64, stride] fp32 slab. S is dZ's row count for
+// wgrad(), net 0's for wgrad_pair().
+WgradNet check_wgrad_net(const char* op, const torch::Tensor& dZ,
+                         const torch::Tensor& X, const torch::Tensor& slab,
+                         int64_t dW_off, int64_t db_off, int64_t n_valid,
+                         int64_t S) {
+  CHK(dZ, torch::kBFloat16);
+  CHK(X, torch::kBFloat16);
+  CHK(slab, torch::kFloat32);
+  TORCH_CHECK(dZ.dim() == 2 && X.dim() == 2, op, ": operands must be 2-D");
+  TORCH_CHECK(dZ.size(0) == S && X.size(0) == S, op, ": dZ/X row mismatch");
+  TORCH_CHECK(S % (4 * 32) == 0, op, ": S must be a multiple of 128");
+  const int64_t K = X.size(1);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= dZ.size(1), op,
+              ": n_valid must be in [1, dZ width]");
+  TORCH_CHECK(slab.dim() == 2 && slab.size(0) >= 64, op,
+              ": slab must be [>=64, stride]");
+  TORCH_CHECK(dW_off >= 0 && dW_off + n_valid * K <= slab.size(1), op,
+              ": dW range outside the slab");
+  TORCH_CHECK(db_off < 0 || db_off + n_valid <= slab.size(1), op,
+              ": db range outside the slab");
+  return {dZ.data_ptr(), X.data_ptr(), slab.data_ptr<float>(), (long)dW_off,
+          (long)db_off, (long)slab.size(1), (int)n_valid};
 }
 
 void wgrad(torch::Tensor dZ, torch::Tensor X, torch::Tensor slab,
            int64_t dW_off, int64_t db_off, int64_t n_valid,
            int64_t kpg = 0, int64_t ntb = 0) {
-  CHK(dZ, torch::kBFloat16);
-  CHK(X, torch::kBFloat16);
-  CHK(slab, torch::kFloat32);
-  int S = dZ.size(0), N_STRIDE = dZ.size(1), K = X.size(1);
-  TORCH_CHECK(X.size(0) == S, "wgrad: dZ/X row mismatch");
-  TORCH_CHECK(S % (4 * 32) == 0, "wgrad: S must be a multiple of 128");
-  long stride = slab.size(1);
-  launch_wgrad(dZ.data_ptr(), X.data_ptr(), slab.data_ptr<float>(),
-               (long)dW_off, (long)db_off, stride, S, N_STRIDE, K,
-               (int)n_valid, (int)kpg, (int)ntb, cur_stream());
-}
-
-void slab_reduce(torch::Tensor slab, torch::Tensor grad16,
-                 torch::Tensor sqnorm, torch::Tensor step_t) {
-  CHK(slab, torch::kFloat32);
-  CHK(grad16, torch::kBFloat16);
-  float* sq = sqnorm.numel() > 0 ? sqnorm.data_ptr<float>() : nullptr;
-  long* st = step_t.numel() > 0 ? step_t.data_ptr<long>() : nullptr;
-  launch_slab_reduce(slab.data_ptr<float>(), grad16.data_ptr(),
-                     slab.size(1), grad16.numel(), sq, st, cur_stream());
+  const int64_t S = dZ.dim() == 2 ? dZ.size(0) : -1;
+  const WgradNet n =
+      check_wgrad_net("wgrad", dZ, X, slab, dW_off, db_off, n_valid, S);
+  launch_wgrad(n.dZ, n.X, n.slab, n.dW_off, n.db_off, n.slab_stride, (int)S,
+               (int)dZ.size(1), (int)X.size(1), n.N_VALID, (int)kpg, (int)ntb,
+               cur_stream());
 }
 
 // Both nets' dW = dZ^T @ X and db = colsum(dZ) in one launch of the
 // pipelined kernel (wgrad.hip); bit-equal to two wgrad() calls. Returns true
 // if the paired kernel covered the shape, false if the launcher fell back to
 // the old kernels.
-static void wgrad_pair_slab_check(const torch::Tensor& slab, int64_t dW_off,
-                                  int64_t db_off, int64_t nv, int64_t K) {
-  TORCH_CHECK(slab.dim() == 2 && slab.size(0) >= 64,
-              "wgrad_pair: slab must be [>=64, stride]");
-  TORCH_CHECK(nv >= 1, "wgrad_pair: n_valid must be >= 1");
-  TORCH_CHECK(dW_off >= 0 && dW_off + nv * K <= slab.size(1),
-              "wgrad_pair: dW range outside the slab");
-  TORCH_CHECK(db_off < 0 || db_off + nv <= slab.size(1),
-              "wgrad_pair: db range outside the slab");
-}
-
 bool wgrad_pair(torch::Tensor dZ0, torch::Tensor X0, torch::Tensor slab0,
                 int64_t dW_off0, int64_t db_off0, int64_t n_valid0,
                 torch::Tensor dZ1, torch::Tensor X1, torch::Tensor slab1,
                 int64_t dW_off1, int64_t db_off1, int64_t n_valid1,
                 int64_t variant = -1) {
-  CHK(dZ0, torch::kBFloat16);
-  CHK(X0, torch::kBFloat16);
-  CHK(slab0, torch::kFloat32);
-  CHK(dZ1, torch::kBFloat16);
-  CHK(X1, torch::kBFloat16);
-  CHK(slab1, torch::kFloat32);
-  TORCH_CHECK(dZ0.dim() == 2 && X0.dim() == 2 && dZ1.dim() == 2 &&
-                  X1.dim() == 2, "wgrad_pair: operands must be 2-D");
-  int64_t S = dZ0.size(0), N_STRIDE = dZ0.size(1), K = X0.size(1);
-  TORCH_CHECK(X0.size(0) == S && dZ1.size(0) == S && X1.size(0) == S,
-              "wgrad_pair: dZ/X row mismatch");
+  const char* op = "wgrad_pair";
+  const int64_t S = dZ0.dim() == 2 ? dZ0.size(0) : -1;
+  const WgradNet n0 =
+      check_wgrad_net(op, dZ0, X0, slab0, dW_off0, db_off0, n_valid0, S);
+  const WgradNet n1 =
+      check_wgrad_net(op, dZ1, X1, slab1, dW_off1, db_off1, n_valid1, S);
+  const int64_t N_STRIDE = dZ0.size(1), K = X0.size(1);
   TORCH_CHECK(dZ1.size(1) == N_STRIDE && X1.size(1) == K,
               "wgrad_pair: the two nets' operand widths differ");
-  TORCH_CHECK(S % (4 * 32) == 0, "wgrad_pair: S must be a multiple of 128");
   TORCH_CHECK(K % 32 == 0, "wgrad_pair: K must be a multiple of 32");
-  TORCH_CHECK(N_STRIDE % 16 == 0, "wgrad_pair: dZ width must be a multiple of 16");
-  TORCH_CHECK(n_valid0 <= N_STRIDE && n_valid1 <= N_STRIDE,
-              "wgrad_pair: n_valid exceeds the dZ width");
-  wgrad_pair_slab_check(slab0, dW_off0, db_off0, n_valid0, K);
-  wgrad_pair_slab_check(slab1, dW_off1, db_off1, n_valid1, K);
-  return launch_wgrad_pair(
-             dZ0.data_ptr(), X0.data_ptr(), slab0.data_ptr<float>(),
-             (long)dW_off0, (long)db_off0, (long)slab0.size(1), (int)n_valid0,
-             dZ1.data_ptr(), X1.data_ptr(), slab1.data_ptr<float>(),
-             (long)dW_off1, (long)db_off1, (long)slab1.size(1), (int)n_valid1,
-             (int)S, (int)N_STRIDE, (int)K, (int)variant, cur_stream()) != 0;
+  TORCH_CHECK(N_STRIDE % 16 == 0,
+              "wgrad_pair: dZ width must be a multiple of 16");
+  return launch_wgrad_pair(n0, n1, (int)S, (int)N_STRIDE, (int)K, (int)variant,
+                           cur_stream()) != 0;
+}
+
+// The largest chain the two-launch tail takes: beyond it the norm kernel of
+// fused_adam_bf16 (2048 blocks of 256 threads, one 8-vector per thread)
+// goes grid-stride and the order of its adds is another one.
+constexpr int64_t kTailMaxN = 2048LL * 256 * 8;
+
+// One chain of a slab reduce: the [64, stride] slab, its flat bf16 grad and
+// the Adam prologue's sqnorm / step_t (both empty: no prologue). With a
+// `counter` the chain is slab_reduce_norm_pair's, whose ordered norm needs
+// 1 + ceil(n / 512) floats of sqnorm and one int32 that is zero between
+// calls.
+TailChain check_reduce_chain(const char* op, const torch::Tensor& slab,
+                             const torch::Tensor& grad,
+                             const torch::Tensor& sqnorm,
+                             const torch::Tensor& step,
+                             const torch::Tensor* counter = nullptr) {
+  CHK(slab, torch::kFloat32);
+  CHK(grad, torch::kBFloat16);
+  TORCH_CHECK(slab.dim() == 2 && slab.size(0) == 64, op,
+              ": slabs must be [64, n]");
+  const int64_t n = grad.numel();
+  TORCH_CHECK(n <= slab.size(1), op, ": grad longer than a slab image");
+  TORCH_CHECK((sqnorm.numel() > 0) == (step.numel() > 0), op,
+              ": sqnorm and step_t go together");
+  if (counter) {
+    CHK(sqnorm, torch::kFloat32);
+    CHK(step, torch::kInt64);
+    CHK(*counter, torch::kInt32);
+    TORCH_CHECK(n >= 1 && n <= kTailMaxN, op,
+                ": grad empty or too long for the ordered norm");
+    TORCH_CHECK(sqnorm.numel() >= 1 + (n + 511) / 512, op,
+                ": sqnorm needs 1 + ceil(n / 512) floats");
+    TORCH_CHECK(step.numel() == 1 && counter->numel() == 1, op,
+                ": step_t and counter hold one element");
+  }
+  return {slab.data_ptr<float>(), grad.data_ptr(), (long)slab.size(1), (long)n,
+          fptr_or_null(sqnorm), ptr_or_null<long>(step),
+          counter ? (unsigned int*)counter->data_ptr<int>() : nullptr};
+}
+
+void slab_reduce(torch::Tensor slab, torch::Tensor grad16,
+                 torch::Tensor sqnorm, torch::Tensor step_t) {
+  const TailChain c =
+      check_reduce_chain("slab_reduce", slab, grad16, sqnorm, step_t);
+  // this kernel zeroes the slab behind its sums
+  launch_slab_reduce(slab.data_ptr<float>(), c.grad16, c.slab_stride, c.n,
+                     c.sqnorm, c.step_t, cur_stream());
 }
 
 // One launch over both chains' slabs; same sums and Adam prologue as
@@ -836,73 +682,51 @@ void slab_reduce_pair(torch::Tensor slab0, torch::Tensor grad0,
                       torch::Tensor sqnorm0, torch::Tensor step0,
                       torch::Tensor slab1, torch::Tensor grad1,
                       torch::Tensor sqnorm1, torch::Tensor step1) {
-  CHK(slab0, torch::kFloat32);
-  CHK(grad0, torch::kBFloat16);
-  CHK(slab1, torch::kFloat32);
-  CHK(grad1, torch::kBFloat16);
-  TORCH_CHECK(slab0.dim() == 2 && slab0.size(0) == 64 && slab1.dim() == 2 &&
-                  slab1.size(0) == 64, "slab_reduce_pair: slabs must be [64, n]");
-  TORCH_CHECK(grad0.numel() <= slab0.size(1) && grad1.numel() <= slab1.size(1),
-              "slab_reduce_pair: grad longer than a slab image");
-  TORCH_CHECK((sqnorm0.numel() > 0) == (step0.numel() > 0) &&
-                  (sqnorm1.numel() > 0) == (step1.numel() > 0),
-              "slab_reduce_pair: sqnorm and step_t go together");
-  float* sq0 = sqnorm0.numel() > 0 ? sqnorm0.data_ptr<float>() : nullptr;
-  long* st0 = step0.numel() > 0 ? step0.data_ptr<long>() : nullptr;
-  float* sq1 = sqnorm1.numel() > 0 ? sqnorm1.data_ptr<float>() : nullptr;
-  long* st1 = step1.numel() > 0 ? step1.data_ptr<long>() : nullptr;
-  launch_slab_reduce_pair(slab0.data_ptr<float>(), grad0.data_ptr(),
-                          slab0.size(1), grad0.numel(), sq0, st0,
-                          slab1.data_ptr<float>(), grad1.data_ptr(),
-                          slab1.size(1), grad1.numel(), sq1, st1,
-                          cur_stream());
+  const char* op = "slab_reduce_pair";
+  launch_slab_reduce_pair(
+      check_reduce_chain(op, slab0, grad0, sqnorm0, step0),
+      check_reduce_chain(op, slab1, grad1, sqnorm1, step1), cur_stream());
 }
-
-// The largest chain the two-launch tail takes: beyond it the norm kernel of
-// fused_adam_bf16 (2048 blocks of 256 threads, one 8-vector per thread)
-// goes grid-stride and the order of its adds is another one.
-constexpr int64_t kTailMaxN = 2048LL * 256 * 8;
 
 // slab_reduce_pair plus each chain's squared gradient norm, left in
 // sqnorm[0] with the bit pattern fused_adam_bf16's ordered norm gives.
-// sqnorm needs 1 + ceil(n / 512) floats, counter is one int32 that is zero
-// between calls.
 void slab_reduce_norm_pair(torch::Tensor slab0, torch::Tensor grad0,
                            torch::Tensor sqnorm0, torch::Tensor step0,
                            torch::Tensor counter0, torch::Tensor slab1,
                            torch::Tensor grad1, torch::Tensor sqnorm1,
                            torch::Tensor step1, torch::Tensor counter1) {
-  CHK(slab0, torch::kFloat32);
-  CHK(grad0, torch::kBFloat16);
-  CHK(sqnorm0, torch::kFloat32);
-  CHK(step0, torch::kInt64);
-  CHK(counter0, torch::kInt32);
-  CHK(slab1, torch::kFloat32);
-  CHK(grad1, torch::kBFloat16);
-  CHK(sqnorm1, torch::kFloat32);
-  CHK(step1, torch::kInt64);
-  CHK(counter1, torch::kInt32);
-  TORCH_CHECK(slab0.dim() == 2 && slab0.size(0) == 64 && slab1.dim() == 2 &&
-                  slab1.size(0) == 64,
-              "slab_reduce_norm_pair: slabs must be [64, n]");
-  const int64_t n0 = grad0.numel(), n1 = grad1.numel();
-  TORCH_CHECK(n0 >= 1 && n1 >= 1 && n0 <= slab0.size(1) && n1 <= slab1.size(1),
-              "slab_reduce_norm_pair: grad empty or longer than a slab image");
-  TORCH_CHECK(n0 <= kTailMaxN && n1 <= kTailMaxN,
-              "slab_reduce_norm_pair: chain too long for the ordered norm");
-  TORCH_CHECK(sqnorm0.numel() >= 1 + (n0 + 511) / 512 &&
-                  sqnorm1.numel() >= 1 + (n1 + 511) / 512,
-              "slab_reduce_norm_pair: sqnorm needs 1 + ceil(n / 512) floats");
-  TORCH_CHECK(step0.numel() == 1 && step1.numel() == 1 &&
-                  counter0.numel() == 1 && counter1.numel() == 1,
-              "slab_reduce_norm_pair: step_t and counter hold one element");
+  const char* op = "slab_reduce_norm_pair";
   launch_slab_reduce_norm_pair(
-      slab0.data_ptr<float>(), grad0.data_ptr(), slab0.size(1), n0,
-      sqnorm0.data_ptr<float>(), step0.data_ptr<long>(),
-      (unsigned int*)counter0.data_ptr<int>(), slab1.data_ptr<float>(),
-      grad1.data_ptr(), slab1.size(1), n1, sqnorm1.data_ptr<float>(),
-      step1.data_ptr<long>(), (unsigned int*)counter1.data_ptr<int>(),
+      check_reduce_chain(op, slab0, grad0, sqnorm0, step0, &counter0),
+      check_reduce_chain(op, slab1, grad1, sqnorm1, step1, &counter1),
       cur_stream());
+}
+
+// One chain of adam_pair: fp32 master param and moments, bf16 grad and
+// (optional) bf16 mirror of one length, the finished norm in sqnorm[0].
+AdamChain check_adam_chain(const torch::Tensor& param,
+                           const torch::Tensor& grad, const torch::Tensor& m,
+                           const torch::Tensor& v, const torch::Tensor& sqnorm,
+                           const torch::Tensor& step,
+                           const torch::Tensor& param_bf16, double lr) {
+  CHK(param, torch::kFloat32);
+  CHK(grad, torch::kBFloat16);
+  CHK(m, torch::kFloat32);
+  CHK(v, torch::kFloat32);
+  CHK(sqnorm, torch::kFloat32);
+  CHK(step, torch::kInt64);
+  const int64_t n = param.numel();
+  TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n,
+              "adam_pair: param, grad and moments must have one length");
+  TORCH_CHECK(sqnorm.numel() >= 1 && step.numel() == 1,
+              "adam_pair: sqnorm and step_t must not be empty");
+  if (param_bf16.numel() > 0) {
+    CHK(param_bf16, torch::kBFloat16);
+    TORCH_CHECK(param_bf16.numel() == n, "adam_pair: bf16 mirror length");
+  }
+  return {param.data_ptr<float>(), grad.data_ptr(), m.data_ptr<float>(),
+          v.data_ptr<float>(), sqnorm.data_ptr<float>(), step.data_ptr<long>(),
+          vptr_or_null(param_bf16), (long)n, (float)lr};
 }
 
 // Both chains' clip + Adam + bf16 mirror in one launch, reading the
@@ -914,45 +738,13 @@ void adam_pair(torch::Tensor param0, torch::Tensor grad0, torch::Tensor m0,
                torch::Tensor sqnorm1, torch::Tensor step1,
                torch::Tensor param_bf16_1, double lr1, double beta1,
                double beta2, double eps, double max_norm, double grad_scale) {
-  CHK(param0, torch::kFloat32);
-  CHK(grad0, torch::kBFloat16);
-  CHK(m0, torch::kFloat32);
-  CHK(v0, torch::kFloat32);
-  CHK(sqnorm0, torch::kFloat32);
-  CHK(step0, torch::kInt64);
-  CHK(param1, torch::kFloat32);
-  CHK(grad1, torch::kBFloat16);
-  CHK(m1, torch::kFloat32);
-  CHK(v1, torch::kFloat32);
-  CHK(sqnorm1, torch::kFloat32);
-  CHK(step1, torch::kInt64);
-  const int64_t n0 = param0.numel(), n1 = param1.numel();
-  TORCH_CHECK(grad0.numel() == n0 && m0.numel() == n0 && v0.numel() == n0 &&
-                  grad1.numel() == n1 && m1.numel() == n1 && v1.numel() == n1,
-              "adam_pair: param, grad and moments must have one length");
-  TORCH_CHECK(sqnorm0.numel() >= 1 && sqnorm1.numel() >= 1 &&
-                  step0.numel() == 1 && step1.numel() == 1,
-              "adam_pair: sqnorm and step_t must not be empty");
-  void* pbf0 = nullptr;
-  void* pbf1 = nullptr;
-  if (param_bf16_0.numel() > 0) {
-    CHK(param_bf16_0, torch::kBFloat16);
-    TORCH_CHECK(param_bf16_0.numel() == n0, "adam_pair: bf16 mirror length");
-    pbf0 = param_bf16_0.data_ptr();
-  }
-  if (param_bf16_1.numel() > 0) {
-    CHK(param_bf16_1, torch::kBFloat16);
-    TORCH_CHECK(param_bf16_1.numel() == n1, "adam_pair: bf16 mirror length");
-    pbf1 = param_bf16_1.data_ptr();
-  }
-  launch_adam_pair(param0.data_ptr<float>(), grad0.data_ptr(),
-                   m0.data_ptr<float>(), v0.data_ptr<float>(),
-                   sqnorm0.data_ptr<float>(), step0.data_ptr<long>(), pbf0, n0,
-                   (float)lr0, param1.data_ptr<float>(), grad1.data_ptr(),
-                   m1.data_ptr<float>(), v1.data_ptr<float>(),
-                   sqnorm1.data_ptr<float>(), step1.data_ptr<long>(), pbf1, n1,
-                   (float)lr1, (float)beta1, (float)beta2, (float)eps,
-                   (float)max_norm, (float)grad_scale, cur_stream());
+  launch_adam_pair(
+      check_adam_chain(param0, grad0, m0, v0, sqnorm0, step0, param_bf16_0,
+                       lr0),
+      check_adam_chain(param1, grad1, m1, v1, sqnorm1, step1, param_bf16_1,
+                       lr1),
+      (float)beta1, (float)beta2, (float)eps, (float)max_norm,
+      (float)grad_scale, cur_stream());
 }
 
 void bump_add(torch::Tensor draw_buf, int64_t n) {
@@ -1221,9 +1013,9 @@ void rnn_scan(torch::Tensor Xp, torch::Tensor Whh, torch::Tensor bhh,
   launch_rnn_scan(
       Xp.data_ptr<float>(), Whh.data_ptr(), bhh.data_ptr<float>(),
       resets.data_ptr<unsigned char>(), h0.data_ptr<float>(),
-      c0.numel() > 0 ? c0.data_ptr<float>() : nullptr,
+      fptr_or_null(c0),
       Hout.data_ptr<float>(), hT.data_ptr<float>(),
-      cT.numel() > 0 ? cT.data_ptr<float>() : nullptr, T, B, H, (int)lstm,
+      fptr_or_null(cT), T, B, H, (int)lstm,
       cur_stream());
 }
 
@@ -1332,9 +1124,6 @@ void snake_step(torch::Tensor grid, torch::Tensor head_r,
   CHK(action, torch::kInt64);
   CHK(length, torch::kInt32);
   int B = grid.size(0);
-  unsigned int* db = draw_buf.numel() > 0
-                         ? (unsigned int*)draw_buf.data_ptr<int>()
-                         : nullptr;
   launch_snake_step(
       grid.data_ptr<int>(), head_r.data_ptr<long>(), head_c.data_ptr<long>(),
       fruit_r.data_ptr<long>(), fruit_c.data_ptr<long>(),
@@ -1346,8 +1135,8 @@ void snake_step(torch::Tensor grid, torch::Tensor head_r,
       discount_out.data_ptr<float>(),
       steptype_out.data_ptr<unsigned char>(),
       done_out.data_ptr<unsigned char>(), B, (int)max_episode_steps,
-      (uint64_t)seed, db, (unsigned int)draw_offset, (int)do_bump,
-      cur_stream());
+      (uint64_t)seed, draw_or_null(draw_buf), (unsigned int)draw_offset,
+      (int)do_bump, cur_stream());
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1377,10 +1166,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "scatter leaf priorities + repair ancestors (device sum-tree)");
   m.def("sumtree_sample", &sumtree_sample,
         "stratified proportional sum-tree descent");
-  m.def("cartpole_step", &cartpole_step, "fused CartPole env step");
-  m.def("ant_step", &ant_step, "fused Ant env step");
+  m.def("cartpole_step", &env_step<long, launch_cartpole_step>,
+        "fused CartPole env step");
+  m.def("ant_step", &env_step<float, launch_ant_step>, "fused Ant env step");
   m.def("ant_reset", &ant_reset, "Ant reset");
-  m.def("humanoid_step", &humanoid_step, "fused Humanoid env step");
+  m.def("humanoid_step", &env_step<float, launch_humanoid_step>,
+        "fused Humanoid env step");
   m.def("gae", &gae, "truncation-aware GAE reverse scan");
   m.def("lambda_returns", &lambda_returns, "lambda returns reverse scan");
   m.def("vtrace", &vtrace, "vtrace errors + pg advantage");

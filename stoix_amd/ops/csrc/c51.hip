@@ -39,6 +39,7 @@
 // themselves e^x small; the softmax normalisation divides the same rounded
 // terms by their own sum, so the mass is unaffected.
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_bf16.h>
 
 typedef __bf16 bf16_t;

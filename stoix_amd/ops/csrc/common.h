@@ -64,16 +64,32 @@ DEV_INLINE void box_muller(float u1, float u2, float* n1, float* n2) {
   *n2 = r * s;
 }
 
+// ------------------------------------- shared by optim.hip and wgrad.hip
+// Sum over the 64 lanes of a wave, left in lane 0: the fixed add order of
+// every ordered gradient norm.
+DEV_INLINE float wave_sum_down(float acc) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  return acc;
+}
+
+// Fused Adam prologue, run by one thread of the grid: zero the norm
+// accumulator and bump the step counter.
+DEV_INLINE void adam_prologue(float* sqnorm, long* step_t) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *sqnorm = 0.0f;
+    *step_t += 1;
+  }
+}
+
+// Blocks of a flat grid-stride launch: ceil(n / threads) in [1, cap].
+inline int flat_blocks(long n, int threads, int cap = 2048) {
+  long want = (n + threads - 1) / threads;
+  return (int)(want < cap ? (want > 0 ? want : 1) : cap);
+}
+
 // step-type codes (stoix_amd.types.StepType)
 #define ST_FIRST 0
 #define ST_MID 1
 #define ST_TERMINATED 2
 #define ST_TRUNCATED 3
-
-#define HIP_CHECK(x)                                                           \
-  do {                                                                         \
-    hipError_t _e = (x);                                                       \
-    if (_e != hipSuccess) {                                                    \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); \
-    }                                                                          \
-  } while (0)

@@ -8,6 +8,7 @@
 // substreams keyed by (seed, env, step_counter) so replayed hip graphs stay
 // deterministic per seed.
 #include "common.h"
+#include "launchers.h"
 #include "ant_core.h"
 
 // ---------------------------------------------------------------- CartPole
@@ -388,13 +389,7 @@ extern "C" __global__ void bump_u32_kernel(unsigned int* p) {
 }
 
 // ----------------------------------------------------------- host launchers
-extern "C" void launch_cartpole_step(
-    float* state, const long* action, int* step_count, float* ep_return,
-    int* ep_length, float* last_ep_return, int* last_ep_length, float* obs_out,
-    float* next_obs_out, float* reward_out, float* discount_out,
-    unsigned char* steptype_out, unsigned char* done_out, int B,
-    int max_episode_steps, uint64_t seed, unsigned int* draw_buf,
-    unsigned int draw_offset, int do_bump, void* stream) {
+extern "C" void launch_cartpole_step(ENV_STEP_PARAMS(long)) {
   int threads = 64;
   int blocks = (B + threads - 1) / threads;
   hipLaunchKernelGGL(cartpole_step_kernel, dim3(blocks), dim3(threads), 0,
@@ -408,13 +403,7 @@ extern "C" void launch_cartpole_step(
                        (hipStream_t)stream, draw_buf);
 }
 
-extern "C" void launch_ant_step(
-    float* state, const float* action, int* step_count, float* ep_return,
-    int* ep_length, float* last_ep_return, int* last_ep_length, float* obs_out,
-    float* next_obs_out, float* reward_out, float* discount_out,
-    unsigned char* steptype_out, unsigned char* done_out, int B,
-    int max_episode_steps, uint64_t seed, unsigned int* draw_buf,
-    unsigned int draw_offset, int do_bump, void* stream) {
+extern "C" void launch_ant_step(ENV_STEP_PARAMS(float)) {
   // 4 threads per env (quad-cooperative physics), 64-thread blocks
   int threads = 64;
   int blocks = (B * 4 + threads - 1) / threads;
@@ -429,13 +418,7 @@ extern "C" void launch_ant_step(
                        (hipStream_t)stream, draw_buf);
 }
 
-extern "C" void launch_humanoid_step(
-    float* state, const float* action, int* step_count, float* ep_return,
-    int* ep_length, float* last_ep_return, int* last_ep_length, float* obs_out,
-    float* next_obs_out, float* reward_out, float* discount_out,
-    unsigned char* steptype_out, unsigned char* done_out, int B,
-    int max_episode_steps, uint64_t seed, unsigned int* draw_buf,
-    unsigned int draw_offset, int do_bump, void* stream) {
+extern "C" void launch_humanoid_step(ENV_STEP_PARAMS(float)) {
   int threads = 64;
   int blocks = (B + threads - 1) / threads;
   hipLaunchKernelGGL(humanoid_step_kernel, dim3(blocks), dim3(threads), 0,

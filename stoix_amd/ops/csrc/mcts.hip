@@ -48,6 +48,7 @@
 // or parent outside the range counts as none, and a tree whose selection is
 // outside it is left as it was.
 #include "common.h"
+#include "launchers.h"
 
 #pragma clang fp contract(off)
 

@@ -41,6 +41,7 @@
 // runtime width onto the same instantiations {128, 256, 512} of every
 // templated kernel.
 #include "common.h"
+#include "launchers.h"
 #include "ant_core.h"
 #include <hip/hip_bf16.h>
 #include <stdexcept>
@@ -790,17 +791,10 @@ extern "C" void launch_linear_silu(const void* X, const void* W,
                                    int S, int K, int N, int do_silu,
                                    void* stream) {
   dim3 grid(S / LSF_BM, N / 128), block(256);
-  if (do_silu) {
-    hipLaunchKernelGGL(linear_silu_kernel<true>, grid, block, 0,
-                       (hipStream_t)stream, (const bf16_t*)X,
-                       (const bf16_t*)W, bias, (bf16_t*)Z, (bf16_t*)H, S, K,
-                       N);
-  } else {
-    hipLaunchKernelGGL(linear_silu_kernel<false>, grid, block, 0,
-                       (hipStream_t)stream, (const bf16_t*)X,
-                       (const bf16_t*)W, bias, (bf16_t*)Z, (bf16_t*)H, S, K,
-                       N);
-  }
+  auto kernel = do_silu ? linear_silu_kernel<true> : linear_silu_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream,
+                     (const bf16_t*)X, (const bf16_t*)W, bias, (bf16_t*)Z,
+                     (bf16_t*)H, S, K, N);
 }
 
 // ------------------------- both nets' layer-1 Linear+SiLU in one launch
@@ -835,13 +829,8 @@ extern "C" void launch_linear_silu(const void* X, const void* W,
 // rows need it is known at compile time (odd 8-row steps).
 //
 // The tile aliases the X staging buffers: one barrier between the last
-// MFMA and the first epilogue write.
-struct LinSiluNet {
-  const bf16_t* W;    // [N, K] row-major
-  const float* bias;  // [N]
-  bf16_t* Z;          // [S, N]
-  bf16_t* H;          // [S, N]
-};
+// MFMA and the first epilogue write. A net's operands arrive as a LinSiluNet
+// (launchers.h).
 
 #define LSP_TILE_BYTES (64 * 128)
 
@@ -893,7 +882,7 @@ __launch_bounds__(256, 2) __global__ void linear_silu_pair_kernel(
   typedef bf16_t ATile[LSF_BM][LSF_BK + LSF_APAD];
   ATile* A = reinterpret_cast<ATile*>(smem);
   const LinSiluNet net = blockIdx.z ? net1 : net0;
-  const bf16_t* __restrict__ W = net.W;
+  const bf16_t* __restrict__ W = (const bf16_t*)net.W;
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   const int m0 = blockIdx.x * LSF_BM;
@@ -965,21 +954,17 @@ __launch_bounds__(256, 2) __global__ void linear_silu_pair_kernel(
   __syncthreads();  // every wave is done with the staged X
   unsigned char* tile = smem + wid * LSP_TILE_BYTES;
   const long o = (long)(m0 + wm) * N + n_blk + wn;
-  lsp_store_tile<false>(acc, tile, net.Z + o, N, lane);
-  lsp_store_tile<true>(acc, tile, net.H + o, N, lane);
+  lsp_store_tile<false>(acc, tile, (bf16_t*)net.Z + o, N, lane);
+  lsp_store_tile<true>(acc, tile, (bf16_t*)net.H + o, N, lane);
 }
 
 // Returns 0 after the launch, 1 for a shape the kernel does not take.
-extern "C" int launch_linear_silu_pair(const void* X, const void* W0,
-                                       const float* b0, void* Z0, void* H0,
-                                       const void* W1, const float* b1,
-                                       void* Z1, void* H1, int S, int K, int N,
-                                       void* stream) {
+extern "C" int launch_linear_silu_pair(const void* X, const LinSiluNet& n0,
+                                       const LinSiluNet& n1, int S, int K,
+                                       int N, void* stream) {
   if (S <= 0 || S % LSF_BM != 0 || N <= 0 || N % 128 != 0 || K <= 0 ||
       K % LSF_BK != 0)
     return 1;
-  LinSiluNet n0{(const bf16_t*)W0, b0, (bf16_t*)Z0, (bf16_t*)H0};
-  LinSiluNet n1{(const bf16_t*)W1, b1, (bf16_t*)Z1, (bf16_t*)H1};
   dim3 grid(S / LSF_BM, N / 128, 2), block(256);
   hipLaunchKernelGGL(linear_silu_pair_kernel, grid, block, 0,
                      (hipStream_t)stream, (const bf16_t*)X, n0, n1, S, K, N);
@@ -1538,10 +1523,7 @@ static void bump_draw(unsigned int* draw_buf, int do_bump, hipStream_t s) {
 }
 
 // Grid of the 8-wide grid-stride SiLU kernels (256 threads per block).
-static dim3 silu_grid(long n) {
-  long want = (n / 8 + 255) / 256;
-  return dim3((unsigned)(want < 4096 ? (want > 0 ? want : 1) : 4096));
-}
+static dim3 silu_grid(long n) { return dim3(flat_blocks(n / 8, 256, 4096)); }
 
 // Grid of the gather kernels: one wave per row, 4 rows per 256-thread block.
 static dim3 gather_grid(int mb_size) { return dim3((mb_size + 3) / 4); }
@@ -1632,11 +1614,10 @@ extern "C" void launch_ppo_head_loss(
     const void* heads, const void* v_in, const float* action,
     const float* old_logp, const float* old_value, const float* adv,
     const float* targets, void* dhead, void* dv_out, void* dv16_out,
-    float* metrics, int B,
-    int ACT, float clip_eps, float ent_coef, float vf_coef, float min_scale,
-    float aff_scale, float aff_shift, float log_aff_scale, uint64_t seed,
-    unsigned int* draw_buf, unsigned int draw_offset, int do_bump,
-    void* stream) {
+    float* metrics, int B, int ACT, float clip_eps, float ent_coef,
+    float vf_coef, float min_scale, float aff_scale, float aff_shift,
+    float log_aff_scale, uint64_t seed, unsigned int* draw_buf,
+    unsigned int draw_offset, int do_bump, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   int threads = 256;
   int blocks = (B + threads - 1) / threads;
@@ -1644,9 +1625,9 @@ extern "C" void launch_ppo_head_loss(
                      (const bf16_t*)heads, (const bf16_t*)v_in, action,
                      old_logp, old_value, adv, targets, (bf16_t*)dhead,
                      (bf16_t*)dv_out, (bf16_t*)dv16_out, metrics, B, ACT,
-                     clip_eps, ent_coef,
-                     vf_coef, min_scale, aff_scale, aff_shift, log_aff_scale,
-                     1.0f / (float)B, seed, draw_buf, draw_offset);
+                     clip_eps, ent_coef, vf_coef, min_scale, aff_scale,
+                     aff_shift, log_aff_scale, 1.0f / (float)B, seed, draw_buf,
+                     draw_offset);
   bump_draw(draw_buf, do_bump, s);
 }
 

@@ -7,6 +7,7 @@
 // norm from device memory (no host sync inside the graph), and a polyak
 // target update. All are memory-bound: loads are float4-vectorised.
 #include "common.h"
+#include "launchers.h"
 
 // partial squared-norm: block-level shuffle reduction + one atomic per block
 extern "C" __global__ void grad_sqnorm_kernel(
@@ -21,7 +22,8 @@ extern "C" __global__ void grad_sqnorm_kernel(
     acc += g.x * g.x + g.y * g.y + g.z * g.z + g.w * g.w;
   }
   for (long j = nvec * 4 + tid; j < n; j += stride) acc += grad[j] * grad[j];
-  // wave reduce (wave64)
+  // wave reduce (wave64): wave_sum_down() spelled out, see
+  // grad_sqnorm_bf16_kernel
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
   __shared__ float warp_sums[16];
@@ -70,10 +72,7 @@ extern "C" __global__ void adam_update_kernel(
 
 extern "C" __global__ void adam_prologue_kernel(float* __restrict__ sqnorm,
                                                 long* __restrict__ step_t) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *sqnorm = 0.0f;
-    *step_t += 1;
-  }
+  adam_prologue(sqnorm, step_t);
 }
 
 // bf16-gradient variants for the fused update path (stoix_amd/ops/csrc/
@@ -85,6 +84,33 @@ extern "C" __global__ void adam_prologue_kernel(float* __restrict__ sqnorm,
 #include <hip/hip_bf16.h>
 typedef __bf16 opt_bf16;
 typedef __bf16 opt_bf16x8 __attribute__((ext_vector_type(8)));
+
+// The two pieces adam_update_bf16_kernel and adam_pair_kernel share, which
+// is what keeps the paired tail bit-equal to the single-chain launches.
+
+// Factor on every gradient element, max_norm > 0: grad_scale, times the
+// global-norm clip where the scaled norm sqrt(sq) * grad_scale exceeds it.
+DEV_INLINE float adam_clip_factor(float sq, float max_norm, float grad_scale) {
+  float norm = sqrtf(sq) * grad_scale;
+  return norm > max_norm ? grad_scale * max_norm / (norm + 1e-6f) : grad_scale;
+}
+
+// Element i: moments, fp32 master param, bf16 mirror (if any).
+DEV_INLINE void adam_step_bf16(float* param, const opt_bf16* grad,
+                               float* exp_avg, float* exp_avg_sq,
+                               opt_bf16* param_bf16, long i, float clip,
+                               float lr, float beta1, float beta2, float eps,
+                               float bc1, float bc2) {
+  float g = (float)grad[i] * clip;
+  float m = exp_avg[i] = beta1 * exp_avg[i] + (1.0f - beta1) * g;
+  float v = exp_avg_sq[i] = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;
+  float p = param[i] - lr * (m / bc1) / (sqrtf(v / bc2) + eps);
+  param[i] = p;
+  if (param_bf16) {
+    opt_bf16* mirror = param_bf16 + i;
+    *mirror = (opt_bf16)p;
+  }
+}
 
 // `partials` non-null: block b stores its sum in partials[b] and
 // adam_update_bf16_kernel adds them up in index order, so the norm (hence
@@ -111,6 +137,9 @@ extern "C" __global__ void grad_sqnorm_bf16_kernel(
     float x = (float)grad[j];
     acc += x * x;
   }
+  // wave_sum_down() (common.h) spelled out: through the helper the compiler
+  // orders two instructions of the lane-0 store differently, and this
+  // kernel's code is kept as it was. The adds are the helper's.
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
   __shared__ float warp_sums[16];
@@ -151,8 +180,7 @@ extern "C" __global__ void adam_update_bf16_kernel(
         float acc = 0.0f;
         for (int p = threadIdx.x; p < n_partials; p += 64)
           acc += sqnorm[1 + p];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+        acc = wave_sum_down(acc);
         if (threadIdx.x == 0) {
           total = acc;
           if (blockIdx.x == 0) sqnorm[0] = acc;
@@ -163,20 +191,14 @@ extern "C" __global__ void adam_update_bf16_kernel(
     } else {
       sq = *sqnorm;
     }
-    float norm = sqrtf(sq) * grad_scale;
-    if (norm > max_norm) clip = grad_scale * max_norm / (norm + 1e-6f);
+    clip = adam_clip_factor(sq, max_norm, grad_scale);
   }
   long t = *step_t;
   float bc1 = 1.0f - powf(beta1, (float)t);
   float bc2 = 1.0f - powf(beta2, (float)t);
-  for (; i < n; i += stride) {
-    float g = (float)grad[i] * clip;
-    float m = exp_avg[i] = beta1 * exp_avg[i] + (1.0f - beta1) * g;
-    float v = exp_avg_sq[i] = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;
-    float p = param[i] - lr * (m / bc1) / (sqrtf(v / bc2) + eps);
-    param[i] = p;
-    if (param_bf16) param_bf16[i] = (opt_bf16)p;
-  }
+  for (; i < n; i += stride)
+    adam_step_bf16(param, grad, exp_avg, exp_avg_sq, param_bf16, i, clip, lr,
+                   beta1, beta2, eps, bc1, bc2);
 }
 
 extern "C" void launch_fused_adam_bf16(float* param, const void* grad,
@@ -197,8 +219,7 @@ extern "C" void launch_fused_adam_bf16(float* param, const void* grad,
     hipLaunchKernelGGL(adam_prologue_kernel, dim3(1), dim3(1), 0, s, sqnorm,
                        step_t);
   int threads = 256;
-  long want = (n / 8 + threads - 1) / threads;
-  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
+  int blocks = flat_blocks(n / 8, threads);
   int n_partials = 0;
   if (max_norm > 0.0f) {
     bool ordered = sqnorm_len >= 1 + (long)blocks;
@@ -207,78 +228,43 @@ extern "C" void launch_fused_adam_bf16(float* param, const void* grad,
                        0, s, (const opt_bf16*)grad, sqnorm,
                        ordered ? sqnorm + 1 : (float*)nullptr, n);
   }
-  long want2 = (n + threads - 1) / threads;
-  int blocks2 = (int)(want2 < 2048 ? (want2 > 0 ? want2 : 1) : 2048);
-  hipLaunchKernelGGL(adam_update_bf16_kernel, dim3(blocks2), dim3(threads), 0,
-                     s, param, (const opt_bf16*)grad, exp_avg, exp_avg_sq,
-                     sqnorm, step_t, (opt_bf16*)param_bf16, n, lr, beta1,
-                     beta2, eps, max_norm, grad_scale, n_partials);
+  hipLaunchKernelGGL(adam_update_bf16_kernel, dim3(flat_blocks(n, threads)),
+                     dim3(threads), 0, s, param, (const opt_bf16*)grad,
+                     exp_avg, exp_avg_sq, sqnorm, step_t,
+                     (opt_bf16*)param_bf16, n, lr, beta1, beta2, eps, max_norm,
+                     grad_scale, n_partials);
 }
 
-// Both chains' clip + Adam in one launch (blockIdx.y picks the chain), for
-// the two-launch optimiser tail: slab_reduce_norm_pair (wgrad.hip) has left
-// the finished squared norm in sqnorm[0], so this is
-// adam_update_bf16_kernel's n_partials == 0 form, element for element.
-struct AdamChain {
-  float* param;
-  const opt_bf16* grad;
-  float* exp_avg;
-  float* exp_avg_sq;
-  const float* sqnorm;
-  const long* step_t;
-  opt_bf16* param_bf16;  // or null
-  long n;
-  float lr;
-};
-
+// Both chains' clip + Adam in one launch (blockIdx.y picks the chain, an
+// AdamChain of launchers.h), for the two-launch optimiser tail:
+// slab_reduce_norm_pair (wgrad.hip) has left the finished squared norm in
+// sqnorm[0], so this is adam_update_bf16_kernel's n_partials == 0 form, by
+// the same adam_clip_factor() and adam_step_bf16().
 extern "C" __global__ void adam_pair_kernel(AdamChain c0, AdamChain c1,
                                             float beta1, float beta2,
                                             float eps, float max_norm,
                                             float grad_scale) {
   const AdamChain c = blockIdx.y ? c1 : c0;
-  float* __restrict__ param = c.param;
-  const opt_bf16* __restrict__ grad = c.grad;
-  float* __restrict__ exp_avg = c.exp_avg;
-  float* __restrict__ exp_avg_sq = c.exp_avg_sq;
-  opt_bf16* __restrict__ param_bf16 = c.param_bf16;
-  const long n = c.n;
-  const float lr = c.lr;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
   float clip = grad_scale;
-  if (max_norm > 0.0f) {
-    float sq = *c.sqnorm;
-    float norm = sqrtf(sq) * grad_scale;
-    if (norm > max_norm) clip = grad_scale * max_norm / (norm + 1e-6f);
-  }
+  if (max_norm > 0.0f)
+    clip = adam_clip_factor(*c.sqnorm, max_norm, grad_scale);
   long t = *c.step_t;
   float bc1 = 1.0f - powf(beta1, (float)t);
   float bc2 = 1.0f - powf(beta2, (float)t);
-  for (; i < n; i += stride) {
-    float g = (float)grad[i] * clip;
-    float m = exp_avg[i] = beta1 * exp_avg[i] + (1.0f - beta1) * g;
-    float v = exp_avg_sq[i] = beta2 * exp_avg_sq[i] + (1.0f - beta2) * g * g;
-    float p = param[i] - lr * (m / bc1) / (sqrtf(v / bc2) + eps);
-    param[i] = p;
-    if (param_bf16) param_bf16[i] = (opt_bf16)p;
-  }
+  for (; i < c.n; i += stride)
+    adam_step_bf16(c.param, (const opt_bf16*)c.grad, c.exp_avg, c.exp_avg_sq,
+                   (opt_bf16*)c.param_bf16, i, clip, c.lr, beta1, beta2, eps,
+                   bc1, bc2);
 }
 
-extern "C" void launch_adam_pair(
-    float* param0, const void* grad0, float* exp_avg0, float* exp_avg_sq0,
-    const float* sqnorm0, const long* step0, void* param_bf16_0, long n0,
-    float lr0, float* param1, const void* grad1, float* exp_avg1,
-    float* exp_avg_sq1, const float* sqnorm1, const long* step1,
-    void* param_bf16_1, long n1, float lr1, float beta1, float beta2,
-    float eps, float max_norm, float grad_scale, void* stream) {
-  AdamChain c0{param0, (const opt_bf16*)grad0, exp_avg0, exp_avg_sq0, sqnorm0,
-               step0, (opt_bf16*)param_bf16_0, n0, lr0};
-  AdamChain c1{param1, (const opt_bf16*)grad1, exp_avg1, exp_avg_sq1, sqnorm1,
-               step1, (opt_bf16*)param_bf16_1, n1, lr1};
+extern "C" void launch_adam_pair(const AdamChain& c0, const AdamChain& c1,
+                                 float beta1, float beta2, float eps,
+                                 float max_norm, float grad_scale,
+                                 void* stream) {
   int threads = 256;
-  long nmax = n0 > n1 ? n0 : n1;
-  long want = (nmax + threads - 1) / threads;
-  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
+  int blocks = flat_blocks(c0.n > c1.n ? c0.n : c1.n, threads);
   hipLaunchKernelGGL(adam_pair_kernel, dim3(blocks, 2), dim3(threads), 0,
                      (hipStream_t)stream, c0, c1, beta1, beta2, eps, max_norm,
                      grad_scale);
@@ -303,24 +289,19 @@ extern "C" void launch_fused_adam(float* param, const float* grad,
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(adam_prologue_kernel, dim3(1), dim3(1), 0, s, sqnorm, step_t);
   int threads = 256;
-  long want = (n / 4 + threads - 1) / threads;
-  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
   if (max_norm > 0.0f) {
-    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(blocks), dim3(threads), 0, s,
-                       grad, sqnorm, n);
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(flat_blocks(n / 4, threads)),
+                       dim3(threads), 0, s, grad, sqnorm, n);
   }
-  long want2 = (n + threads - 1) / threads;
-  int blocks2 = (int)(want2 < 2048 ? (want2 > 0 ? want2 : 1) : 2048);
-  hipLaunchKernelGGL(adam_update_kernel, dim3(blocks2), dim3(threads), 0, s,
-                     param, grad, exp_avg, exp_avg_sq, sqnorm, step_t, n, lr,
-                     beta1, beta2, eps, max_norm);
+  hipLaunchKernelGGL(adam_update_kernel, dim3(flat_blocks(n, threads)),
+                     dim3(threads), 0, s, param, grad, exp_avg, exp_avg_sq,
+                     sqnorm, step_t, n, lr, beta1, beta2, eps, max_norm);
 }
 
 extern "C" void launch_polyak(const float* online, float* target, long n,
                               float tau, void* stream) {
   int threads = 256;
-  long want = (n + threads - 1) / threads;
-  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
-  hipLaunchKernelGGL(polyak_kernel, dim3(blocks), dim3(threads), 0,
+  hipLaunchKernelGGL(polyak_kernel, dim3(flat_blocks(n, threads)),
+                     dim3(threads), 0,
                      (hipStream_t)stream, online, target, n, tau);
 }

@@ -26,6 +26,7 @@
 // tree levels are a few KB and stay L2/L1-resident, so the walk is
 // latency- not bandwidth-bound; one launch replaces ~depth torch gathers.
 #include "common.h"
+#include "launchers.h"
 
 // The tree and the draws are compared bit for bit with the torch path, which
 // rounds after every operation: no FMA contraction in this file.

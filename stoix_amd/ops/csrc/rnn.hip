@@ -25,6 +25,7 @@
 // below, the reverse scan that turns dHout into dXp, dHg and dh0/dc0
 // (ops/rnn.py _RnnScan; weight and bias gradients are GEMMs in the caller).
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_bf16.h>
 
 typedef __bf16 bf16_t;

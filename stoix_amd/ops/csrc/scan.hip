@@ -5,6 +5,7 @@
 // bench shapes (T=128, B=4096) the whole pass is a single ~100 us-scale
 // launch replacing a 128-step Python loop.
 #include "common.h"
+#include "launchers.h"
 
 extern "C" __global__ void gae_kernel(
     const float* __restrict__ r_t,        // [T, B]

@@ -14,6 +14,7 @@
 // differ by construction, parity tests resync on eat/reset like the
 // CartPole reset-noise protocol).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 constexpr int R = 12, C = 12, NC = R * C;

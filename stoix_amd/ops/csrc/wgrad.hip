@@ -19,6 +19,7 @@
 // PPO engine runs by default: the same sums, both nets per launch, tiles
 // staged row-major and read transposed, loads pipelined behind the MFMAs.
 #include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 #include <hip/hip_bf16.h>
 
@@ -164,14 +165,15 @@ extern "C" __global__ void slab_reduce_kernel(float* __restrict__ slab,
                                               long slab_stride, long n,
                                               float* __restrict__ sqnorm,
                                               long* __restrict__ step_t) {
-  // fused Adam prologue (zero the norm accumulator, bump the step counter)
-  // rides along: this kernel always runs right before the chain's Adam
-  if (sqnorm && blockIdx.x == 0 && threadIdx.x == 0) {
-    *sqnorm = 0.0f;
-    *step_t += 1;
-  }
+  // fused Adam prologue rides along: this kernel always runs right before
+  // the chain's Adam
+  if (sqnorm) adam_prologue(sqnorm, step_t);
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
+  // The same ascending sum as slab_sum() below, kept as its own interleaved
+  // load/add/zero loop on purpose: this is the knob-off reference, and its
+  // memory pattern is part of what the A/B against the paired kernels
+  // compares.
   for (; i < n; i += stride) {
     float s = 0.0f;
 #pragma unroll
@@ -205,13 +207,8 @@ extern "C" __global__ void slab_reduce_kernel(float* __restrict__ slab,
 // o, 2o, 3o (mod 8, o odd), never by 4, and the 128-byte step per 8 rows
 // moves the other four by 32 banks = 4 groups, so the eight 32-byte
 // segments tile the 64 banks: conflict-free by the (a/4)%64 bank rule.
-struct WgradNet {
-  const bf16_t* dZ;  // [S, N_STRIDE]
-  const bf16_t* X;   // [S, K]
-  float* slab;       // [WG_SLICES, slab_stride]
-  long dW_off, db_off, slab_stride;
-  int N_VALID;
-};
+//
+// A net's operands arrive as a WgradNet (launchers.h).
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
@@ -244,8 +241,8 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * (ZB + XB)];
 
   const bool second = blockIdx.z != 0;
-  const bf16_t* __restrict__ dZ = second ? net1.dZ : net0.dZ;
-  const bf16_t* __restrict__ X = second ? net1.X : net0.X;
+  const bf16_t* __restrict__ dZ = (const bf16_t*)(second ? net1.dZ : net0.dZ);
+  const bf16_t* __restrict__ X = (const bf16_t*)(second ? net1.X : net0.X);
   float* __restrict__ slab = second ? net1.slab : net0.slab;
   const long dW_off = second ? net1.dW_off : net0.dW_off;
   const long db_off = second ? net1.db_off : net0.db_off;
@@ -404,9 +401,25 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
   }
 }
 
+// Element i of a chain's gradient: the ascending sum over the WG_SLICES
+// slab images, in slab_reduce_kernel's order. Every paired reduce takes its
+// sums from here.
+DEV_INLINE float slab_sum(const float* __restrict__ slab, long slab_stride,
+                          long i) {
+  // all 64 loads go out before the first add (the compiler left two in
+  // flight when load and add shared one loop); the adds keep their order
+  float v[WG_SLICES];
+#pragma unroll
+  for (int z = 0; z < WG_SLICES; ++z) v[z] = slab[(long)z * slab_stride + i];
+  float s = 0.0f;
+#pragma unroll
+  for (int z = 0; z < WG_SLICES; ++z) s += v[z];
+  return s;
+}
+
 // Both chains' slabs -> their flat bf16 grads in one launch (blockIdx.y
-// picks the chain), same ascending sum over the WG_SLICES images and same
-// fused Adam prologue as slab_reduce_kernel, but NO stores to the slab.
+// picks the chain), slab_sum() and the fused Adam prologue of
+// slab_reduce_kernel (adam_prologue(), common.h), but NO stores to the slab.
 // That is safe wherever the slab is only ever filled by the wgrad kernels
 // with a fixed set of (offset, shape) calls, as in the PPO engine: they
 // store (never accumulate), so every valid element of the used images is
@@ -425,23 +438,11 @@ extern "C" __launch_bounds__(256) __global__ void slab_reduce_pair_kernel(
   const long n = second ? n1 : n0;
   float* sqnorm = second ? sqnorm1 : sqnorm0;
   long* step_t = second ? step1 : step0;
-  if (sqnorm && blockIdx.x == 0 && threadIdx.x == 0) {
-    *sqnorm = 0.0f;
-    *step_t += 1;
-  }
+  if (sqnorm) adam_prologue(sqnorm, step_t);
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    // all 64 loads go out before the first add (the compiler left two in
-    // flight when load and add shared one loop); the adds keep their order
-    float v[WG_SLICES];
-#pragma unroll
-    for (int z = 0; z < WG_SLICES; ++z) v[z] = slab[(long)z * slab_stride + i];
-    float s = 0.0f;
-#pragma unroll
-    for (int z = 0; z < WG_SLICES; ++z) s += v[z];
-    grad16[i] = (__bf16)s;
-  }
+  for (; i < n; i += stride)
+    grad16[i] = (__bf16)slab_sum(slab, slab_stride, i);
 }
 
 // slab_reduce_pair_kernel plus the squared gradient norm of each chain, so
@@ -467,28 +468,9 @@ extern "C" __launch_bounds__(256) __global__ void slab_reduce_pair_kernel(
 // counter for the next launch. No block waits for another, and no float
 // atomic enters the sum. Block 0 recomputes the (at most 7) tail elements
 // from the slab, the same ascending sum, so it needs nothing from the
-// block that owns them.
-struct TailChain {
-  const float* slab;  // [WG_SLICES, slab_stride]
-  __bf16* grad16;     // [n]
-  long slab_stride, n;
-  float* sqnorm;      // [0] = total, [1 + b] = tree sum of block b
-  long* step_t;
-  unsigned int* counter;  // zero between launches
-};
-
-__device__ __forceinline__ float slab_sum(const float* __restrict__ slab,
-                                          long slab_stride, long i) {
-  // all 64 loads go out before the first add; the adds keep their order
-  float v[WG_SLICES];
-#pragma unroll
-  for (int z = 0; z < WG_SLICES; ++z) v[z] = slab[(long)z * slab_stride + i];
-  float s = 0.0f;
-#pragma unroll
-  for (int z = 0; z < WG_SLICES; ++z) s += v[z];
-  return s;
-}
-
+// block that owns them. The trees are wave_sum_down() (common.h), the one
+// adam_update_bf16_kernel sums the norm kernel's partials with. A chain's
+// operands arrive as a TailChain (launchers.h).
 extern "C" __launch_bounds__(512) __global__
     void slab_reduce_norm_pair_kernel(TailChain c0, TailChain c1) {
   const TailChain c = blockIdx.y ? c1 : c0;
@@ -502,7 +484,7 @@ extern "C" __launch_bounds__(512) __global__
   float xv = 0.0f;
   if (i < n) {
     const __bf16 q = (__bf16)slab_sum(c.slab, c.slab_stride, i);
-    c.grad16[i] = q;
+    ((__bf16*)c.grad16)[i] = q;
     xv = (float)q;
   }
   x[threadIdx.x] = xv;
@@ -522,8 +504,7 @@ extern "C" __launch_bounds__(512) __global__
                                         nvec * 8 + threadIdx.x);
       acc += v * v;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    acc = wave_sum_down(acc);
     if (threadIdx.x == 0) {
       // publish the one float write-through and wait for it, then take a
       // ticket. A release fence here would write the whole L2 back, the
@@ -556,6 +537,8 @@ extern "C" __launch_bounds__(512) __global__
     }
     acc += s;
   }
+  // wave_sum_down() spelled out: through the helper the compiler schedules
+  // this kernel differently, and its code is kept as it was
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
   if (threadIdx.x == 0) {
@@ -566,14 +549,10 @@ extern "C" __launch_bounds__(512) __global__
 }
 
 // n0, n1 >= 1; each sqnorm holds 1 + ceil(n / 512) floats (bind.cpp checks)
-extern "C" void launch_slab_reduce_norm_pair(
-    const float* slab0, void* grad0, long stride0, long n0, float* sqnorm0,
-    long* step0, unsigned int* counter0, const float* slab1, void* grad1,
-    long stride1, long n1, float* sqnorm1, long* step1,
-    unsigned int* counter1, void* stream) {
-  TailChain c0{slab0, (__bf16*)grad0, stride0, n0, sqnorm0, step0, counter0};
-  TailChain c1{slab1, (__bf16*)grad1, stride1, n1, sqnorm1, step1, counter1};
-  long nmax = n0 > n1 ? n0 : n1;
+extern "C" void launch_slab_reduce_norm_pair(const TailChain& c0,
+                                             const TailChain& c1,
+                                             void* stream) {
+  long nmax = c0.n > c1.n ? c0.n : c1.n;
   int blocks = (int)((nmax + 511) / 512);
   hipLaunchKernelGGL(slab_reduce_norm_pair_kernel, dim3(blocks, 2), dim3(512),
                      0, (hipStream_t)stream, c0, c1);
@@ -601,6 +580,19 @@ extern "C" __global__ void tr16_probe_kernel(const bf16_t* __restrict__ in,
 }
 
 // --------------------------------------------------------- host launchers
+
+// Wave-slices S is split over: WG_SLICES, or STOIX_WGRAD_SLICES in
+// [4, WG_SLICES], halved until the slices divide S into whole 32-row steps
+// (down to 4).
+static int pick_slices(int S) {
+  int n_slices = WG_SLICES;
+  if (const char* e = getenv("STOIX_WGRAD_SLICES")) {
+    int v = atoi(e);
+    if (v >= 4 && v <= WG_SLICES) n_slices = v;
+  }
+  while (n_slices > 4 && (S % (n_slices * 32)) != 0) n_slices >>= 1;
+  return n_slices;
+}
 
 extern "C" void launch_wgrad(const void* dZ, const void* X, float* slab,
                              long dW_off, long db_off, long slab_stride,
@@ -630,12 +622,7 @@ extern "C" void launch_wgrad(const void* dZ, const void* X, float* slab,
     KPG = 2;
   }
   int KTG = K / (16 * KPG);
-  int n_slices = WG_SLICES;
-  if (const char* e = getenv("STOIX_WGRAD_SLICES")) {
-    int v = atoi(e);
-    if (v >= 4 && v <= WG_SLICES) n_slices = v;
-  }
-  while (n_slices > 4 && (S % (n_slices * 32)) != 0) n_slices >>= 1;
+  int n_slices = pick_slices(S);
   dim3 grid(NT / NTB, KTG, n_slices / 4), block(256);
 #define WGRAD_LAUNCH(KPGV, NTBV)                                            \
   hipLaunchKernelGGL((wgrad_kernel<KPGV, NTBV>), grid, block, 0, s,         \
@@ -659,9 +646,8 @@ extern "C" void launch_slab_reduce(float* slab, void* grad16,
                                    long slab_stride, long n, float* sqnorm,
                                    long* step_t, void* stream) {
   int threads = 256;
-  long want = (n + threads - 1) / threads;
-  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(threads), 0,
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_blocks(n, threads)),
+                     dim3(threads), 0,
                      (hipStream_t)stream, slab, (__bf16*)grad16, slab_stride,
                      n, sqnorm, step_t);
 }
@@ -675,28 +661,18 @@ extern "C" void launch_slab_reduce(float* slab, void* grad16,
 // variant >= 0 picks one of the alternatives the sweep compares. A shape
 // outside this table goes to the old kernels, one launch per net, never to
 // a neighbouring instantiation. Returns 1 if the paired kernel ran.
-extern "C" int launch_wgrad_pair(
-    const void* dZ0, const void* X0, float* slab0, long dW_off0, long db_off0,
-    long stride0, int nv0, const void* dZ1, const void* X1, float* slab1,
-    long dW_off1, long db_off1, long stride1, int nv1, int S, int N_STRIDE,
-    int K, int variant, void* stream) {
+extern "C" int launch_wgrad_pair(const WgradNet& a, const WgradNet& b, int S,
+                                 int N_STRIDE, int K, int variant,
+                                 void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  int n_slices = WG_SLICES;
-  if (const char* e = getenv("STOIX_WGRAD_SLICES")) {
-    int v = atoi(e);
-    if (v >= 4 && v <= WG_SLICES) n_slices = v;
-  }
-  while (n_slices > 4 && (S % (n_slices * 32)) != 0) n_slices >>= 1;
+  const int nv0 = a.N_VALID, nv1 = b.N_VALID;
+  int n_slices = pick_slices(S);
   // variant < 0: the baked winners = variant 0, except layer 2 (K 256/512)
   // = variant 6. variants >= 4: the tiles of variant - 4 with the slice
   // along blockIdx.x (needs n_slices % 8 == 0 to line up with the 8 XCDs)
   if (variant < 0) variant = (K == 256 || K == 512) && N_STRIDE != 16 ? 6 : 0;
   const int slice_major = variant >= 4 && n_slices % 8 == 0;
   if (variant >= 4) variant -= 4;
-  WgradNet a{(const bf16_t*)dZ0, (const bf16_t*)X0, slab0, dW_off0, db_off0,
-             stride0, nv0};
-  WgradNet b{(const bf16_t*)dZ1, (const bf16_t*)X1, slab1, dW_off1, db_off1,
-             stride1, nv1};
 #define WPAIR_LAUNCH(NTW, KTW, WN, WK, SB)                                   \
   do {                                                                       \
     constexpr int TN = WN * NTW * 16, TK = WK * KTW * 16;                    \
@@ -736,25 +712,22 @@ extern "C" int launch_wgrad_pair(
     }
   }
 #undef WPAIR_LAUNCH
-  launch_wgrad(dZ0, X0, slab0, dW_off0, db_off0, stride0, S, N_STRIDE, K, nv0,
-               0, 0, stream);
-  launch_wgrad(dZ1, X1, slab1, dW_off1, db_off1, stride1, S, N_STRIDE, K, nv1,
-               0, 0, stream);
+  for (const WgradNet* n : {&a, &b})
+    launch_wgrad(n->dZ, n->X, n->slab, n->dW_off, n->db_off, n->slab_stride, S,
+                 N_STRIDE, K, n->N_VALID, 0, 0, stream);
   return 0;
 }
 
-extern "C" void launch_slab_reduce_pair(
-    const float* slab0, void* grad0, long stride0, long n0, float* sqnorm0,
-    long* step0, const float* slab1, void* grad1, long stride1, long n1,
-    float* sqnorm1, long* step1, void* stream) {
+// c.counter is not used here
+extern "C" void launch_slab_reduce_pair(const TailChain& c0,
+                                        const TailChain& c1, void* stream) {
   int threads = 256;
-  long nmax = n0 > n1 ? n0 : n1;
-  long want = (nmax + threads - 1) / threads;
-  int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
+  int blocks = flat_blocks(c0.n > c1.n ? c0.n : c1.n, threads);
   hipLaunchKernelGGL(slab_reduce_pair_kernel, dim3(blocks, 2), dim3(threads),
-                     0, (hipStream_t)stream, slab0, (__bf16*)grad0, stride0,
-                     n0, sqnorm0, step0, slab1, (__bf16*)grad1, stride1, n1,
-                     sqnorm1, step1);
+                     0, (hipStream_t)stream, c0.slab, (__bf16*)c0.grad16,
+                     c0.slab_stride, c0.n, c0.sqnorm, c0.step_t, c1.slab,
+                     (__bf16*)c1.grad16, c1.slab_stride, c1.n, c1.sqnorm,
+                     c1.step_t);
 }
 
 extern "C" void launch_tr16_probe(const void* in, float* out, int base_mode,

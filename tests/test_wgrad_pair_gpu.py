@@ -226,6 +226,67 @@ def test_pair_rejections_and_fallback(ext):
                            old[i][written].view(torch.int32))
 
 
+def _small():
+    """S=128, N_STRIDE=16, K=32 operands and the [64, 16*32+16] zero slab of
+    the single-net argument tests: dW at 0, db right behind it, nothing to
+    spare."""
+    S, N, K = 128, 16, 32
+    g = torch.Generator().manual_seed(4242)
+    dZ = (torch.randn(S, N, generator=g) * 0.1).bfloat16().cuda()
+    X = torch.randn(S, K, generator=g).bfloat16().cuda()
+    slab = torch.zeros(64, N * K + N, dtype=torch.float32, device="cuda")
+    return S, N, K, dZ, X, slab
+
+
+@requires_gpu
+@pytest.mark.parametrize("case", ["dW_past_stride", "db_past_stride", "x_rows"])
+def test_wgrad_refuses_out_of_range(ext, case):
+    """wgrad() runs wgrad_pair()'s operand and slab-range checks: a dW or db
+    range that ends past the slab stride, or an X with other rows than dZ,
+    raises in the binding, and nothing was launched: the slab is untouched."""
+    S, N, K, dZ, X, slab = _small()
+    if case == "dW_past_stride":
+        args, msg = (dZ, X, slab, N + 1, -1, N), "dW range"
+    elif case == "db_past_stride":
+        args, msg = (dZ, X, slab, 0, N * K + 1, N), "db range"
+    else:
+        X2 = torch.cat([X, X])
+        args, msg = (dZ, X2, slab, 0, N * K, N), "row mismatch"
+    with pytest.raises(RuntimeError, match=msg):
+        ext.wgrad(*args)
+    torch.cuda.synchronize()
+    assert (slab == 0).all()
+
+
+@requires_gpu
+def test_slab_reduce_refuses_long_grad(ext):
+    """slab_reduce() runs slab_reduce_pair()'s checks: a grad16 longer than a
+    slab image raises before any launch."""
+    _, _, _, _, _, slab = _small()
+    grad16 = torch.zeros(slab.size(1) + 1, dtype=torch.bfloat16, device="cuda")
+    with pytest.raises(RuntimeError, match="longer than a slab image"):
+        ext.slab_reduce(slab, grad16, torch.zeros(0, device="cuda"),
+                        torch.zeros(0, dtype=torch.int64, device="cuda"))
+    torch.cuda.synchronize()
+    assert (slab == 0).all() and (grad16 == 0).all()
+
+
+@requires_gpu
+def test_wgrad_in_range_equals_pair_fallback(ext):
+    """In-range offsets at the same shape still go through: wgrad() fills the
+    slab bit for bit as wgrad_pair()'s fallback does (K = 32 with a 16-wide
+    dZ is outside the paired table, so the fallback is the same kernel)."""
+    S, N, K, dZ, X, slab = _small()
+    ext.wgrad(dZ, X, slab, 0, N * K, N)
+    pair = [torch.zeros_like(slab) for _ in range(2)]
+    assert ext.wgrad_pair(dZ, X, pair[0], 0, N * K, N,
+                          dZ, X, pair[1], 0, N * K, N) is False
+    torch.cuda.synchronize()
+    assert slab[:4].abs().sum().item() > 0 and (slab[4:] == 0).all()
+    for p in pair:
+        assert torch.equal(p.view(torch.int32), slab.view(torch.int32))
+
+
 # ------------------------------------------------------------------ engine
 
 
