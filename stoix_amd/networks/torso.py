@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from stoix_amd.networks.layers import NoisyLinear
 from stoix_amd.networks.utils import get_activation
+from stoix_amd.ops.noisy import act_kind, noisy_linear_fused, noisy_route_to_kernel
 
 
 def orthogonal_init(layer: nn.Linear, scale: float = 2.0**0.5) -> nn.Linear:
@@ -76,7 +77,23 @@ class NoisyMLPTorso(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() > 2 and x.shape[-1] != self._in_dim:
             x = x.reshape(x.shape[0], -1)
-        return self.net(x)
+        # A layer on the fused path (ops/noisy.py) takes the SiLU/ReLU module
+        # that follows it as its kernel epilogue, and hands its pre-activation
+        # to the next fused layer, whose backward then applies act' itself.
+        # With LayerNorm in between the activation stays a module.
+        mods = list(self.net)
+        pre = None
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, NoisyLinear) and noisy_route_to_kernel(x, m):
+                kind = act_kind(mods[i + 1]) if i + 1 < len(mods) else None
+                x, pre = noisy_linear_fused(m, x, kind, pre)
+                i += 2 if kind else 1
+            else:
+                x, pre = m(x), None
+                i += 1
+        return x
 
 
 class CNNTorso(nn.Module):

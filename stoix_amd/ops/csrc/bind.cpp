@@ -861,6 +861,140 @@ void c51_loss_bwd(torch::Tensor grad_ce, torch::Tensor logits_tm1,
                       cur_stream());
 }
 
+// Argument checks shared by the NoisyLinear launchers (noisy.hip): the fp32
+// parameters mu_w / sigma_w [N, K] contiguous and 16-byte aligned, the noise
+// vectors fp32 views of the NoiseBank buffer (any offset, unit stride), and
+// activations / gradients as contiguous, 16-byte aligned fp32 or bf16
+// [rows, cols]. check_noisy_act returns 1 for bf16.
+struct NoisyShape {
+  int64_t N, K;
+};
+
+void check_noisy_f32(const torch::Tensor& t, const char* name, int64_t n) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                  t.numel() == n && t.is_contiguous(),
+              name, " must be a contiguous fp32 GPU tensor of ", n, " values");
+}
+
+NoisyShape check_noisy_params(const torch::Tensor& mu_w,
+                              const torch::Tensor& sigma_w,
+                              const torch::Tensor& eps_in,
+                              const torch::Tensor& eps_out) {
+  TORCH_CHECK(mu_w.dim() == 2, "mu_w must be [N, K]");
+  const NoisyShape s{mu_w.size(0), mu_w.size(1)};
+  check_noisy_f32(mu_w, "mu_w", s.N * s.K);
+  check_noisy_f32(sigma_w, "sigma_w", s.N * s.K);
+  check_noisy_f32(eps_in, "eps_in", s.K);
+  check_noisy_f32(eps_out, "eps_out", s.N);
+  TORCH_CHECK((uintptr_t)mu_w.data_ptr() % 16 == 0 &&
+                  (uintptr_t)sigma_w.data_ptr() % 16 == 0,
+              "mu_w and sigma_w must be 16-byte aligned");
+  return s;
+}
+
+int check_noisy_act(const torch::Tensor& t, const char* name, int64_t rows,
+                    int64_t cols) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  (uintptr_t)t.data_ptr() % 16 == 0,
+              name, " must be a contiguous, 16-byte aligned GPU tensor");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 ||
+                  t.scalar_type() == torch::kBFloat16,
+              name, " must be fp32 or bf16");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols, name,
+              " must be [", rows, ", ", cols, "]");
+  return t.scalar_type() == torch::kBFloat16 ? 1 : 0;
+}
+
+// An optional bf16 [rows, cols] tensor (empty = absent) -> pointer or null.
+void* noisy_opt_bf16(const torch::Tensor& t, const char* name, int64_t rows,
+                     int64_t cols) {
+  if (t.numel() == 0) return nullptr;
+  TORCH_CHECK(check_noisy_act(t, name, rows, cols) == 1, name,
+              " must be bf16");
+  return t.data_ptr();
+}
+
+// Z / H: empty tensors are not written. False for an ineligible shape.
+bool noisy_linear_fwd(torch::Tensor X, torch::Tensor mu_w,
+                      torch::Tensor sigma_w, torch::Tensor mu_b,
+                      torch::Tensor sigma_b, torch::Tensor eps_in,
+                      torch::Tensor eps_out, torch::Tensor Z, torch::Tensor H,
+                      int64_t act, bool noisy) {
+  const NoisyShape s = check_noisy_params(mu_w, sigma_w, eps_in, eps_out);
+  TORCH_CHECK(X.dim() == 2, "X must be [S, K]");
+  const int64_t S = X.size(0);
+  const int x_bf16 = check_noisy_act(X, "X", S, s.K);
+  check_noisy_f32(mu_b, "mu_b", s.N);
+  check_noisy_f32(sigma_b, "sigma_b", s.N);
+  void* zp = noisy_opt_bf16(Z, "Z", S, s.N);
+  void* hp = noisy_opt_bf16(H, "H", S, s.N);
+  TORCH_CHECK(zp || hp, "noisy_linear_fwd needs Z or H");
+  TORCH_CHECK(act != 0 || zp, "noisy_linear_fwd without activation writes Z");
+  return launch_noisy_linear_fwd(
+             X.data_ptr(), mu_w.data_ptr<float>(), sigma_w.data_ptr<float>(),
+             mu_b.data_ptr<float>(), sigma_b.data_ptr<float>(),
+             eps_in.data_ptr<float>(), eps_out.data_ptr<float>(), zp, hp,
+             (int)S, (int)s.K, (int)s.N, x_bf16, (int)act, noisy ? 1 : 0,
+             cur_stream()) == 0;
+}
+
+// out = dZ @ W, times act_prev'(Z_prev) when act_prev != 0.
+bool noisy_linear_dgrad(torch::Tensor dZ, torch::Tensor mu_w,
+                        torch::Tensor sigma_w, torch::Tensor eps_in,
+                        torch::Tensor eps_out, torch::Tensor Z_prev,
+                        torch::Tensor out, int64_t act_prev, bool noisy) {
+  const NoisyShape s = check_noisy_params(mu_w, sigma_w, eps_in, eps_out);
+  TORCH_CHECK(dZ.dim() == 2, "dZ must be [S, N]");
+  const int64_t S = dZ.size(0);
+  const int dz_bf16 = check_noisy_act(dZ, "dZ", S, s.N);
+  void* zp = noisy_opt_bf16(Z_prev, "Z_prev", S, s.K);
+  TORCH_CHECK(act_prev == 0 || zp, "act_prev needs Z_prev");
+  TORCH_CHECK(noisy_opt_bf16(out, "out", S, s.K), "out must be bf16 [S, K]");
+  return launch_noisy_linear_dgrad(
+             dZ.data_ptr(), mu_w.data_ptr<float>(), sigma_w.data_ptr<float>(),
+             eps_in.data_ptr<float>(), eps_out.data_ptr<float>(), zp,
+             out.data_ptr(), (int)S, (int)s.K, (int)s.N, dz_bf16,
+             (int)act_prev, noisy ? 1 : 0, cur_stream()) == 0;
+}
+
+// dsigma_w / dsigma_b: empty tensors are not written (noise off).
+bool noisy_linear_wgrad(torch::Tensor dZ, torch::Tensor X,
+                        torch::Tensor eps_in, torch::Tensor eps_out,
+                        torch::Tensor dmu_w, torch::Tensor dsigma_w,
+                        torch::Tensor dmu_b, torch::Tensor dsigma_b) {
+  TORCH_CHECK(dZ.dim() == 2 && X.dim() == 2, "dZ [S, N] and X [S, K]");
+  const int64_t S = dZ.size(0), N = dZ.size(1), K = X.size(1);
+  const int dz_bf16 = check_noisy_act(dZ, "dZ", S, N);
+  const int x_bf16 = check_noisy_act(X, "X", S, K);
+  check_noisy_f32(eps_in, "eps_in", K);
+  check_noisy_f32(eps_out, "eps_out", N);
+  check_noisy_f32(dmu_w, "dmu_w", N * K);
+  check_noisy_f32(dmu_b, "dmu_b", N);
+  float *sw = nullptr, *sb = nullptr;
+  if (dsigma_w.numel() > 0) {
+    check_noisy_f32(dsigma_w, "dsigma_w", N * K);
+    check_noisy_f32(dsigma_b, "dsigma_b", N);
+    sw = dsigma_w.data_ptr<float>();
+    sb = dsigma_b.data_ptr<float>();
+  }
+  if (S < 1 || N < 1 || K < 8 || K % 8 != 0) return false;
+  int slices, s_per;
+  long slab_stride;
+  noisy_wgrad_geometry((int)S, (int)K, (int)N, &slices, &s_per, &slab_stride);
+  torch::Tensor slab = torch::empty(
+      {(int64_t)slices * slab_stride}, dmu_w.options());
+  return launch_noisy_linear_wgrad(
+             dZ.data_ptr(), X.data_ptr(), slab.data_ptr<float>(),
+             eps_in.data_ptr<float>(), eps_out.data_ptr<float>(),
+             dmu_w.data_ptr<float>(), sw, dmu_b.data_ptr<float>(), sb, (int)S,
+             (int)K, (int)N, dz_bf16, x_bf16, cur_stream()) == 0;
+}
+
+void noise_transform(torch::Tensor x) {
+  check_noisy_f32(x, "x", x.numel());
+  launch_noise_transform(x.data_ptr<float>(), (long)x.numel(), cur_stream());
+}
+
 // Argument checks shared by the two MCTS launchers (mcts.hip): the arena of
 // search/mcts.py, contiguous on one GPU, B trees x N node slots x A actions.
 struct MctsShape {
@@ -1148,6 +1282,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "C51 categorical TD loss: softmax + fixed-order projection + CE");
   m.def("c51_loss_bwd", &c51_loss_bwd,
         "C51 categorical TD loss: analytic logits backward");
+  m.def("noisy_linear_fwd", &noisy_linear_fwd,
+        "NoisyLinear forward, the noisy weight formed while staging");
+  m.def("noisy_linear_dgrad", &noisy_linear_dgrad,
+        "NoisyLinear input gradient, optionally times act'(Z_prev)");
+  m.def("noisy_linear_wgrad", &noisy_linear_wgrad,
+        "NoisyLinear mu/sigma weight and bias gradients (split-S + reduce)");
+  m.def("noise_transform", &noise_transform,
+        "in-place f(x) = sign(x) sqrt(|x|) over the NoiseBank buffer");
   m.def("snake_step", &snake_step,
         "fused Snake env step (dynamics + metrics + autoreset + render)");
   m.def("rnn_scan", &rnn_scan,

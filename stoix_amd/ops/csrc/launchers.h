@@ -266,4 +266,27 @@ void launch_mcts_expand_backup(
     const float* reward_new, const float* discount_new, const float* prior_new,
     const float* value_new, int B, int N, int A, int new_node, void* stream);
 
+// ---- noisy.hip. act: 0 none, 1 SiLU, 2 ReLU. noisy = 0 reads mu only. The
+// three GEMM launchers return 0 after the launch, 1 for a shape the kernels
+// do not take (K % 8 != 0, an empty dimension), launching nothing.
+int launch_noisy_linear_fwd(
+    const void* X, const float* mu_w, const float* sigma_w, const float* mu_b,
+    const float* sigma_b, const float* eps_in, const float* eps_out, void* Z,
+    void* H, int S, int K, int N, int x_bf16, int act, int noisy,
+    void* stream);
+int launch_noisy_linear_dgrad(
+    const void* dZ, const float* mu_w, const float* sigma_w,
+    const float* eps_in, const float* eps_out, const void* Z_prev, void* out,
+    int S, int K, int N, int dz_bf16, int act_prev, int noisy, void* stream);
+// Slices of S the wgrad runs with and the fp32 elements of one slab image.
+void noisy_wgrad_geometry(int S, int K, int N, int* slices, int* s_per,
+                          long* slab_stride);
+// slab holds slices * slab_stride floats; dsigma_w / dsigma_b may be null.
+int launch_noisy_linear_wgrad(
+    const void* dZ, const void* X, float* slab, const float* eps_in,
+    const float* eps_out, float* dmu_w, float* dsigma_w, float* dmu_b,
+    float* dsigma_b, int S, int K, int N, int dz_bf16, int x_bf16,
+    void* stream);
+void launch_noise_transform(float* x, long n, void* stream);
+
 }  // extern "C"
