@@ -628,6 +628,112 @@ bool wgrad_pair(torch::Tensor dZ0, torch::Tensor X0, torch::Tensor slab0,
                            cur_stream()) != 0;
 }
 
+// Layer-1 wgrad_pair with the SiLU backward inside: a net's operand is
+// dH * silu'(Z), formed while the kernel stages the tile, so neither the
+// silu_bwd launch nor the dZ buffer is needed. Bit-equal to silu_bwd +
+// wgrad_pair. Returns true after the launch; false = not taken (a Z on one
+// net only, where an empty tensor stands for none, or a shape outside the
+// layer-1 table), nothing launched, the slab untouched: the caller runs
+// silu_bwd + wgrad_pair. Z gets the checks dH gets.
+bool wgrad_pair_act(torch::Tensor dH0, torch::Tensor Z0, torch::Tensor X0,
+                    torch::Tensor slab0, int64_t dW_off0, int64_t db_off0,
+                    int64_t n_valid0, torch::Tensor dH1, torch::Tensor Z1,
+                    torch::Tensor X1, torch::Tensor slab1, int64_t dW_off1,
+                    int64_t db_off1, int64_t n_valid1, int64_t variant = -1) {
+  const char* op = "wgrad_pair_act";
+  const int64_t S = dH0.dim() == 2 ? dH0.size(0) : -1;
+  WgradNet n0 =
+      check_wgrad_net(op, dH0, X0, slab0, dW_off0, db_off0, n_valid0, S);
+  WgradNet n1 =
+      check_wgrad_net(op, dH1, X1, slab1, dW_off1, db_off1, n_valid1, S);
+  const int64_t N_STRIDE = dH0.size(1), K = X0.size(1);
+  TORCH_CHECK(dH1.size(1) == N_STRIDE && X1.size(1) == K,
+              "wgrad_pair_act: the two nets' operand widths differ");
+  TORCH_CHECK(K % 32 == 0, "wgrad_pair_act: K must be a multiple of 32");
+  TORCH_CHECK(N_STRIDE % 16 == 0,
+              "wgrad_pair_act: dH width must be a multiple of 16");
+  auto zact = [&](const torch::Tensor& Z, const torch::Tensor& dH) {
+    if (Z.numel() == 0) return (const void*)nullptr;
+    CHK(Z, torch::kBFloat16);
+    TORCH_CHECK(Z.dim() == 2 && Z.size(0) == S && Z.size(1) == N_STRIDE, op,
+                ": Z must have dH's shape");
+    TORCH_CHECK(Z.device() == dH.device(), op, ": Z on another device");
+    TORCH_CHECK((uintptr_t)Z.data_ptr() % 16 == 0 &&
+                    (uintptr_t)dH.data_ptr() % 16 == 0,
+                op, ": dH and Z must be 16-byte aligned");
+    return (const void*)Z.data_ptr();
+  };
+  n0.Zact = zact(Z0, dH0);
+  n1.Zact = zact(Z1, dH1);
+  if (!n0.Zact && !n1.Zact) return false;
+  return launch_wgrad_pair(n0, n1, (int)S, (int)N_STRIDE, (int)K, (int)variant,
+                           cur_stream()) == 1;
+}
+
+// ppo_gather / ppo_gather_disc for all rows of idx in one bandwidth-built
+// launch (mlp.hip ppo_gather_rows_kernel), outputs bit-equal. action int64
+// [rows] = the discrete form, float [rows, ACT <= 8] the continuous one.
+// Returns false, launching nothing, for a shape the kernel does not take.
+bool ppo_gather_rows(torch::Tensor idx, torch::Tensor obs,
+                     torch::Tensor action, torch::Tensor logp,
+                     torch::Tensor value, torch::Tensor adv,
+                     torch::Tensor targets, torch::Tensor obs_out,
+                     torch::Tensor action_out, torch::Tensor logp_out,
+                     torch::Tensor value_out, torch::Tensor adv_out,
+                     torch::Tensor targets_out, torch::Tensor nmean,
+                     torch::Tensor nvar) {
+  const char* op = "ppo_gather_rows";
+  CHK(idx, torch::kInt64);
+  CHK(obs, torch::kFloat32);
+  CHK(obs_out, torch::kBFloat16);
+  const bool disc = action.scalar_type() == torch::kInt64;
+  const auto act_ty = disc ? torch::kInt64 : torch::kFloat32;
+  CHK(action, act_ty);
+  CHK(action_out, act_ty);
+  const int64_t n = idx.numel();
+  TORCH_CHECK(obs.dim() == 2 && obs_out.dim() == 2 && obs_out.size(0) >= n, op,
+              ": obs [rows, OBS], obs_out [>= n, OBS_PAD]");
+  const int64_t rows = obs.size(0), OBS = obs.size(1), PAD = obs_out.size(1);
+  TORCH_CHECK((uintptr_t)obs_out.data_ptr() % 8 == 0, op,
+              ": obs_out must be 8-byte aligned");
+  int64_t ACT = 1;
+  if (disc) {
+    TORCH_CHECK(action.numel() == rows && action_out.numel() >= n, op,
+                ": discrete action is one int64 per row");
+  } else {
+    TORCH_CHECK(action.dim() == 2 && action.size(0) == rows &&
+                    action_out.dim() == 2 && action_out.size(0) >= n &&
+                    action_out.size(1) == action.size(1),
+                op, ": action [rows, ACT], action_out [>= n, ACT]");
+    ACT = action.size(1);
+  }
+  for (const torch::Tensor* t : {&logp, &value, &adv, &targets}) {
+    CHK(*t, torch::kFloat32);
+    TORCH_CHECK(t->numel() == rows, op, ": a source field per obs row");
+  }
+  for (const torch::Tensor* t :
+       {&logp_out, &value_out, &adv_out, &targets_out}) {
+    CHK(*t, torch::kFloat32);
+    TORCH_CHECK(t->numel() >= n, op, ": an output field shorter than idx");
+  }
+  if (nmean.numel() > 0 || nvar.numel() > 0) {
+    CHK(nmean, torch::kFloat32);
+    CHK(nvar, torch::kFloat32);
+    TORCH_CHECK(nmean.numel() == OBS && nvar.numel() == OBS, op,
+                ": nmean / nvar must hold OBS floats");
+  }
+  if (n == 0) return false;
+  return launch_ppo_gather_rows(
+             idx.data_ptr<long>(), (long)n, obs.data_ptr<float>(), (int)OBS,
+             (int)PAD, action.data_ptr(), (int)ACT, disc ? 1 : 0,
+             logp.data_ptr<float>(), value.data_ptr<float>(),
+             adv.data_ptr<float>(), targets.data_ptr<float>(),
+             obs_out.data_ptr(), action_out.data_ptr(),
+             logp_out.data_ptr<float>(), value_out.data_ptr<float>(),
+             adv_out.data_ptr<float>(), targets_out.data_ptr<float>(),
+             fptr_or_null(nmean), fptr_or_null(nvar), cur_stream()) == 0;
+}
+
 // The largest chain the two-launch tail takes: beyond it the norm kernel of
 // fused_adam_bf16 (2048 blocks of 256 threads, one 8-vector per thread)
 // goes grid-stride and the order of its adds is another one.
@@ -1351,6 +1457,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("db_off0"), py::arg("n_valid0"), py::arg("dZ1"),
         py::arg("X1"), py::arg("slab1"), py::arg("dW_off1"),
         py::arg("db_off1"), py::arg("n_valid1"), py::arg("variant") = -1);
+  m.def("wgrad_pair_act", &wgrad_pair_act,
+        "layer-1 wgrad_pair with dZ = dH * silu'(Z) formed in the staging; "
+        "false = not taken, nothing launched",
+        py::arg("dH0"), py::arg("Z0"), py::arg("X0"), py::arg("slab0"),
+        py::arg("dW_off0"), py::arg("db_off0"), py::arg("n_valid0"),
+        py::arg("dH1"), py::arg("Z1"), py::arg("X1"), py::arg("slab1"),
+        py::arg("dW_off1"), py::arg("db_off1"), py::arg("n_valid1"),
+        py::arg("variant") = -1);
+  m.def("ppo_gather_rows", &ppo_gather_rows,
+        "ppo_gather / ppo_gather_disc for a whole epoch's rows in one "
+        "launch; false = shape not taken, nothing launched");
   m.def("slab_reduce_pair", &slab_reduce_pair,
         "both chains' slabs -> flat bf16 grads, slabs left un-zeroed");
   m.def("linear_silu_pair", &linear_silu_pair,

@@ -64,6 +64,24 @@ DEV_INLINE void box_muller(float u1, float u2, float* n1, float* n2) {
   *n2 = r * s;
 }
 
+// Kernels added since the packed-fp32 finding (see ops/build.py on noisy.hip)
+// carry this attribute: no v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 in
+// their code, whatever flags the rest of the file is built with. Per-element
+// results are the same either way.
+#define NO_PK_FP32 __attribute__((target("no-packed-fp32-ops")))
+
+// ------------------------------------- shared by mlp.hip and wgrad.hip
+// SiLU and its derivative: one definition for the forward/backward passes of
+// mlp.hip and for the layer-1 wgrad that forms dZ = dH * silu'(Z) itself.
+DEV_INLINE float silu_f(float x) {
+  float s = 1.0f / (1.0f + __expf(-x));
+  return x * s;
+}
+DEV_INLINE float silu_grad_f(float x) {
+  float s = 1.0f / (1.0f + __expf(-x));
+  return s * (1.0f + x * (1.0f - s));
+}
+
 // ------------------------------------- shared by optim.hip and wgrad.hip
 // Sum over the 64 lanes of a wave, left in lane 0: the fixed add order of
 // every ordered gradient norm.

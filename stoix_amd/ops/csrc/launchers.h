@@ -19,6 +19,9 @@ struct WgradNet {
   float* slab;     // [WG_SLICES, slab_stride]
   long dW_off, db_off, slab_stride;  // db_off < 0: no bias sum
   int N_VALID;
+  // null: dZ is the operand. Else bf16 [S, N_STRIDE], the pre-activation of
+  // the layer, and the operand is dZ * silu'(Zact), formed while staging.
+  const void* Zact;
 };
 
 // One chain's slab reduce into its flat bf16 grad.
@@ -122,7 +125,11 @@ void launch_wgrad(const void* dZ, const void* X, float* slab, long dW_off,
                   void* stream);
 void launch_slab_reduce(float* slab, void* grad16, long slab_stride, long n,
                         float* sqnorm, long* step_t, void* stream);
-// Returns 1 if the paired kernel ran, 0 after the per-net fallback.
+// Returns 1 if the paired kernel ran, 0 after the per-net fallback. With a
+// Zact on either net there is no fallback: the fused kernel runs (1) when
+// both nets carry one and the shape is a layer-1 shape, else nothing is
+// launched and the call returns WGRAD_PAIR_NOT_TAKEN.
+#define WGRAD_PAIR_NOT_TAKEN (-1)
 int launch_wgrad_pair(const WgradNet& net0, const WgradNet& net1, int S,
                       int N_STRIDE, int K, int variant, void* stream);
 void launch_slab_reduce_pair(const TailChain& c0, const TailChain& c1,
@@ -201,6 +208,17 @@ void launch_ppo_gather_disc(
     const float* adv, const float* targets, void* obs_out, long* action_out,
     float* logp_out, float* value_out, float* adv_out, float* targets_out,
     const float* nmean, const float* nvar, void* stream);
+// The two gathers above for n rows at once, built for bandwidth (8 lanes per
+// row, 32 rows per wave): same outputs bit for bit. OBS_PAD in {32, 64, 96,
+// 128}. action / action_out are float [., ACT] (ACT 1..8), or with disc != 0
+// one int64 per row. Returns 0 after the launch, 1 for a shape it does not
+// take, launching nothing.
+int launch_ppo_gather_rows(
+    const long* idx, long n, const float* obs, int OBS, int OBS_PAD,
+    const void* action, int ACT, int disc, const float* logp,
+    const float* value, const float* adv, const float* targets, void* obs_out,
+    void* action_out, float* logp_out, float* value_out, float* adv_out,
+    float* targets_out, const float* nmean, const float* nvar, void* stream);
 void launch_ppo_head_loss(
     const void* heads, const void* v_in, const float* action,
     const float* old_logp, const float* old_value, const float* adv,

@@ -58,14 +58,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 DEV_INLINE float bf2f(bf16_t x) { return (float)x; }
 DEV_INLINE bf16_t f2bf(float x) { return (bf16_t)x; }
 
-DEV_INLINE float silu_f(float x) {
-  float s = 1.0f / (1.0f + __expf(-x));
-  return x * s;
-}
-DEV_INLINE float silu_grad_f(float x) {
-  float s = 1.0f / (1.0f + __expf(-x));
-  return s * (1.0f + x * (1.0f - s));
-}
+// silu_f / silu_grad_f: common.h
 DEV_INLINE float softplus_f(float x) {
   // log1p(exp(x)) stable
   return (x > 20.0f) ? x : log1pf(__expf(x));
@@ -1805,6 +1798,139 @@ extern "C" __global__ void ppo_gather_disc_kernel(
                   nvar, [=](long src, int row, int lane) {
                     if (lane == 0) action_out[row] = action[src];
                   });
+}
+
+// ------------------------------------------------- gather for a whole epoch
+// The outputs of ppo_gather_kernel / ppo_gather_disc_kernel for n rows, bit
+// for bit (same normalise_obs, same f2bf, same zero fill of the pad
+// columns), built for bandwidth where those are one wave per row behind the
+// load of idx[row]: 8 lanes per row, 8 rows per pass, 4 passes = 32 rows per
+// wave. The four idx loads of a lane go out first, then every load that
+// depends on them (per lane 16 * NCH obs dwords and at most 8 more), so a
+// wave has 32 rows' reads in flight before its first store. Lane l of a row
+// group takes the 4-column chunks l, l + 8, ... of the OBS_PAD = 32 * NCH
+// columns: a store instruction leaves the wave as eight 64-byte runs, whole
+// obs_out rows at OBS_PAD = 32. Obs rows are only 4-byte aligned (OBS is
+// any), so the obs loads are dwords. Lanes 0..3 of the group also carry one
+// scalar field each (logp, value, adv, targets), lanes 4..7 the action
+// (elements l - 4 and l of a continuous row; lane 4 the int64 of a discrete
+// one). Rows >= n load row idx 0's sources (in bounds) and store nothing.
+template <int NCH, bool DISC>
+__launch_bounds__(256) __global__ NO_PK_FP32 void ppo_gather_rows_kernel(
+    const long* __restrict__ idx, long n, const float* __restrict__ obs,
+    int OBS, const void* __restrict__ action_v, int ACT,
+    const float* __restrict__ logp, const float* __restrict__ value,
+    const float* __restrict__ adv, const float* __restrict__ targets,
+    bf16_t* __restrict__ obs_out, void* __restrict__ action_out_v,
+    float* __restrict__ logp_out, float* __restrict__ value_out,
+    float* __restrict__ adv_out, float* __restrict__ targets_out,
+    const float* __restrict__ nmean, const float* __restrict__ nvar) {
+  constexpr int OBS_PAD = 32 * NCH, PASS = 4;
+  const int lane = threadIdx.x & 63;
+  const int l = lane & 7;
+  const long row0 =
+      ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (8 * PASS) + (lane >> 3);
+  const float* __restrict__ fsrc =
+      l == 0 ? logp : l == 1 ? value : l == 2 ? adv : targets;
+  float* __restrict__ fdst =
+      l == 0 ? logp_out : l == 1 ? value_out : l == 2 ? adv_out : targets_out;
+  const float* __restrict__ action = (const float*)action_v;
+  const long* __restrict__ action_l = (const long*)action_v;
+
+  long src[PASS];
+#pragma unroll
+  for (int p = 0; p < PASS; ++p) {
+    const long row = row0 + 8 * p;
+    src[p] = row < n ? idx[row] : idx[0];
+  }
+  float v[PASS][NCH][4], sc[PASS], a0[PASS], a1[PASS];
+  long al[PASS];
+#pragma unroll
+  for (int p = 0; p < PASS; ++p) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = (c * 8 + l) * 4 + j;
+        v[p][c][j] = k < OBS ? obs[src[p] * OBS + k] : 0.0f;
+      }
+    sc[p] = l < 4 ? fsrc[src[p]] : 0.0f;
+    if (DISC) {
+      al[p] = l == 4 ? action_l[src[p]] : 0;
+    } else {
+      a0[p] = l >= 4 && l - 4 < ACT ? action[src[p] * ACT + l - 4] : 0.0f;
+      a1[p] = l >= 4 && l < ACT ? action[src[p] * ACT + l] : 0.0f;
+    }
+  }
+  float mean[NCH][4], var[NCH][4];
+  if (nmean) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = (c * 8 + l) * 4 + j;
+        mean[c][j] = k < OBS ? nmean[k] : 0.0f;
+        var[c][j] = k < OBS ? nvar[k] : 1.0f;
+      }
+  }
+#pragma unroll
+  for (int p = 0; p < PASS; ++p) {
+    const long row = row0 + 8 * p;
+    if (row >= n) continue;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = (c * 8 + l) * 4 + j;
+        float x = v[p][c][j];
+        if (nmean && k < OBS) x = normalise_obs(x, mean[c][j], var[c][j]);
+        o[j] = f2bf(x);
+      }
+      *reinterpret_cast<bf16x4*>(obs_out + row * OBS_PAD + (c * 8 + l) * 4) =
+          o;
+    }
+    if (l < 4) fdst[row] = sc[p];
+    if (DISC) {
+      if (l == 4) ((long*)action_out_v)[row] = al[p];
+    } else {
+      float* __restrict__ ao = (float*)action_out_v + row * ACT;
+      if (l >= 4 && l - 4 < ACT) ao[l - 4] = a0[p];
+      if (l >= 4 && l < ACT) ao[l] = a1[p];
+    }
+  }
+}
+
+extern "C" int launch_ppo_gather_rows(
+    const long* idx, long n, const float* obs, int OBS, int OBS_PAD,
+    const void* action, int ACT, int disc, const float* logp,
+    const float* value, const float* adv, const float* targets, void* obs_out,
+    void* action_out, float* logp_out, float* value_out, float* adv_out,
+    float* targets_out, const float* nmean, const float* nvar, void* stream) {
+  if (n < 1 || OBS < 1 || OBS > OBS_PAD || OBS_PAD % 32 != 0 || OBS_PAD > 128)
+    return 1;
+  if (!disc && (ACT < 1 || ACT > 8)) return 1;
+  dim3 grid((unsigned)((n + 127) / 128)), block(256);
+#define GATHER_ROWS(NCH, DISC)                                              \
+  hipLaunchKernelGGL((ppo_gather_rows_kernel<NCH, DISC>), grid, block, 0,   \
+                     (hipStream_t)stream, idx, n, obs, OBS, action, ACT,    \
+                     logp, value, adv, targets, (bf16_t*)obs_out,           \
+                     action_out, logp_out, value_out, adv_out, targets_out, \
+                     nmean, nvar)
+  const int nch = OBS_PAD / 32;
+  if (disc) {
+    if (nch == 1) GATHER_ROWS(1, true);
+    else if (nch == 2) GATHER_ROWS(2, true);
+    else if (nch == 3) GATHER_ROWS(3, true);
+    else GATHER_ROWS(4, true);
+  } else {
+    if (nch == 1) GATHER_ROWS(1, false);
+    else if (nch == 2) GATHER_ROWS(2, false);
+    else if (nch == 3) GATHER_ROWS(3, false);
+    else GATHER_ROWS(4, false);
+  }
+#undef GATHER_ROWS
+  return 0;
 }
 
 extern "C" void launch_policy_value_step_disc(

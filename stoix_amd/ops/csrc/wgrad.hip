@@ -224,10 +224,19 @@ __device__ __forceinline__ bf16x8 wp_tr_frag(const unsigned char* p,
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int NTW, int KTW, int WN, int WK, int SB>
-__launch_bounds__(256) __global__ void wgrad_pair_kernel(
-    WgradNet net0, WgradNet net1, int S, int N_STRIDE, int K, int n_slices,
-    int kblocks, int slice_major) {
+//
+// ACT_BWD (wgrad_pair_act_kernel, layer 1): a net's dZ pointer holds dH and
+// Zact the layer's pre-activation; the operand dZ = bf16(dH * silu'(Z)),
+// silu_bwd_kernel's expression element for element, is formed in registers
+// between the prefetch and the LDS write, so dZ never goes through memory.
+// The Z tile is prefetched next to the dH tile (LZ more bf16x8 registers);
+// from the LDS write on nothing differs. Only for tiles that span all of K
+// (kblocks == 1): each dZ element is then staged, and its silu' computed,
+// once.
+template <int NTW, int KTW, int WN, int WK, int SB, bool ACT_BWD>
+DEV_INLINE void wgrad_pair_body(const WgradNet& net0, const WgradNet& net1,
+                                int S, int N_STRIDE, int K, int n_slices,
+                                int kblocks, int slice_major) {
   static_assert(WN * WK == 4, "four waves");
   constexpr int TN = WN * NTW * 16, TK = WK * KTW * 16;
   constexpr int CZ = TN / 8, CX = TK / 8;  // 16-byte chunks per tile row
@@ -243,6 +252,8 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
   const bool second = blockIdx.z != 0;
   const bf16_t* __restrict__ dZ = (const bf16_t*)(second ? net1.dZ : net0.dZ);
   const bf16_t* __restrict__ X = (const bf16_t*)(second ? net1.X : net0.X);
+  const bf16_t* __restrict__ Zact =
+      (const bf16_t*)(second ? net1.Zact : net0.Zact);
   float* __restrict__ slab = second ? net1.slab : net0.slab;
   const long dW_off = second ? net1.dW_off : net0.dW_off;
   const long db_off = second ? net1.db_off : net0.db_off;
@@ -286,6 +297,7 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
   const int xl = (8 * g + q) * PX + g * 128 + (wk * KTW * 16 + 4 * p) * 2;
 
   bf16x8 rz[LZ], rx[LX];  // register prefetch of one stage
+  bf16x8 ra[ACT_BWD ? LZ : 1];  // the Z tile that goes with rz (dH)
 
   auto gload = [&](int st) {
     const int r0 = s_begin + st * ROWS;
@@ -299,6 +311,9 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
         gr = gr < s_end ? gr : s_end - 1;
         rz[i] = *reinterpret_cast<const bf16x8*>(
             dZ + (long)gr * N_STRIDE + n0 + (c % CZ) * 8);
+        if constexpr (ACT_BWD)
+          ra[i] = *reinterpret_cast<const bf16x8*>(
+              Zact + (long)gr * N_STRIDE + n0 + (c % CZ) * 8);
       }
     }
 #pragma unroll
@@ -320,6 +335,12 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
       const int c = tid + i * 256;
       if (NZ % 256 == 0 || c < NZ) {
         const int row = c / CZ;
+        if constexpr (ACT_BWD) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            rz[i][j] =
+                (bf16_t)((float)rz[i][j] * silu_grad_f((float)ra[i][j]));
+        }
         *reinterpret_cast<bf16x8*>(zb + row * PZ + (row >> 3) * 128 +
                                    (c % CZ) * 16) = rz[i];
       }
@@ -399,6 +420,22 @@ __launch_bounds__(256) __global__ void wgrad_pair_kernel(
       if (g == 0 && nb + col < N_VALID) out[db_off + nb + col] = d;
     }
   }
+}
+
+template <int NTW, int KTW, int WN, int WK, int SB>
+__launch_bounds__(256) __global__ void wgrad_pair_kernel(
+    WgradNet net0, WgradNet net1, int S, int N_STRIDE, int K, int n_slices,
+    int kblocks, int slice_major) {
+  wgrad_pair_body<NTW, KTW, WN, WK, SB, false>(net0, net1, S, N_STRIDE, K,
+                                               n_slices, kblocks, slice_major);
+}
+
+template <int NTW, int KTW, int WN, int WK, int SB>
+__launch_bounds__(256) __global__ NO_PK_FP32 void wgrad_pair_act_kernel(
+    WgradNet net0, WgradNet net1, int S, int N_STRIDE, int K, int n_slices,
+    int kblocks, int slice_major) {
+  wgrad_pair_body<NTW, KTW, WN, WK, SB, true>(net0, net1, S, N_STRIDE, K,
+                                              n_slices, kblocks, slice_major);
 }
 
 // Element i of a chain's gradient: the ascending sum over the WG_SLICES
@@ -661,6 +698,12 @@ extern "C" void launch_slab_reduce(float* slab, void* grad16,
 // variant >= 0 picks one of the alternatives the sweep compares. A shape
 // outside this table goes to the old kernels, one launch per net, never to
 // a neighbouring instantiation. Returns 1 if the paired kernel ran.
+//
+// Zact on a net asks for the fused layer-1 form (wgrad_pair_act_kernel): the
+// tiles of the K in {32, 64, 96, 128} rows above (variant 1 at K = 32: one
+// step a stage, for the sweep). It has no fallback, since the old kernels
+// would take dH for dZ: Zact on one net only, or a shape outside those rows,
+// launches nothing and returns WGRAD_PAIR_NOT_TAKEN.
 extern "C" int launch_wgrad_pair(const WgradNet& a, const WgradNet& b, int S,
                                  int N_STRIDE, int K, int variant,
                                  void* stream) {
@@ -674,19 +717,32 @@ extern "C" int launch_wgrad_pair(const WgradNet& a, const WgradNet& b, int S,
   const int slice_major = variant >= 4 && n_slices % 8 == 0;
   if (variant >= 4) variant -= 4;
 #define WPAIR_LAUNCH(NTW, KTW, WN, WK, SB)                                   \
+  WPAIR_LAUNCH_K(wgrad_pair_kernel, NTW, KTW, WN, WK, SB)
+#define WPAIR_LAUNCH_K(KERNEL, NTW, KTW, WN, WK, SB)                         \
   do {                                                                       \
     constexpr int TN = WN * NTW * 16, TK = WK * KTW * 16;                    \
     int kblocks = K / TK;                                                    \
     int tiles = (N_STRIDE / TN) * kblocks;                                   \
     dim3 grid(slice_major ? n_slices : tiles, slice_major ? tiles : n_slices, \
               2), block(256);                                                \
-    hipLaunchKernelGGL((wgrad_pair_kernel<NTW, KTW, WN, WK, SB>), grid,      \
-                       block, 0, s, a, b, S, N_STRIDE, K, n_slices,          \
-                       kblocks, slice_major);                                \
-    return 1;                                                                \
+    hipLaunchKernelGGL((KERNEL<NTW, KTW, WN, WK, SB>), grid, block, 0, s, a, \
+                       b, S, N_STRIDE, K, n_slices, kblocks, slice_major);   \
+    return 1;                                                               \
   } while (0)
   const bool ok = (S % (n_slices * 32)) == 0 && n_slices % 4 == 0;
   const bool hid = N_STRIDE == 128 || N_STRIDE == 256 || N_STRIDE == 512;
+  if (a.Zact || b.Zact) {
+    if (a.Zact && b.Zact && ok && hid && nv0 == N_STRIDE && nv1 == N_STRIDE) {
+      if (K == 32) {
+        if (variant == 1) WPAIR_LAUNCH_K(wgrad_pair_act_kernel, 2, 2, 4, 1, 1);
+        WPAIR_LAUNCH_K(wgrad_pair_act_kernel, 2, 2, 4, 1, 2);
+      }
+      if (K == 64) WPAIR_LAUNCH_K(wgrad_pair_act_kernel, 2, 4, 4, 1, 2);
+      if (K == 96) WPAIR_LAUNCH_K(wgrad_pair_act_kernel, 2, 6, 4, 1, 1);
+      if (K == 128) WPAIR_LAUNCH_K(wgrad_pair_act_kernel, 8, 2, 1, 4, 1);
+    }
+    return WGRAD_PAIR_NOT_TAKEN;
+  }
   if (ok && N_STRIDE == 16 && nv0 >= 1 && nv0 <= 16 && nv1 >= 1 &&
       nv1 <= 16 && (K == 128 || K == 256 || K == 512)) {
     if (variant == 1) WPAIR_LAUNCH(1, 2, 1, 4, 1);
@@ -712,6 +768,7 @@ extern "C" int launch_wgrad_pair(const WgradNet& a, const WgradNet& b, int S,
     }
   }
 #undef WPAIR_LAUNCH
+#undef WPAIR_LAUNCH_K
   for (const WgradNet* n : {&a, &b})
     launch_wgrad(n->dZ, n->X, n->slab, n->dW_off, n->db_off, n->slab_stride, S,
                  N_STRIDE, K, n->N_VALID, 0, 0, stream);

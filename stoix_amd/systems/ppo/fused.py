@@ -12,7 +12,11 @@ stoix_amd/ops/csrc/mlp.hip:
                  physics + autoreset + bootstrap critic, ONE launch); or
                  policy_value_step -> env HIP step -> value_forward for
                  non-Ant HIP envs
-  minibatch:     ppo_gather -> layer-1 fused linear_silu_pair, both nets in
+  epoch:         ppo_gather_rows, ONE gather over the whole permutation
+                 into epoch-sized buffers; a minibatch reads its row slice
+                 (STOIX_EPOCH_GATHER=0 or S % 4 != 0: ppo_gather per
+                 minibatch)
+  minibatch:     layer-1 fused linear_silu_pair, both nets in
                  one launch over the shared Xmb (custom MFMA wins at K=32,
                  row-contiguous stores) -> layer-2 tuned hipBLASLt GemmAndBias
                  per net (library wins at K=256) -> silu_heads_fwd (ONE
@@ -21,9 +25,11 @@ stoix_amd/ops/csrc/mlp.hip:
                  head bwd; metrics only on the reported minibatch)
                  -> stacked backward over [2, S, H] buffers: heads_bwd_silu
                  (head dgrads formed inside the layer-2 silu backward),
-                 one silu_bwd for layer 1, dH1 as one batched bmm against the
-                 adjacent-W2 [2, H, H] view, split-K wgrads into per-chain
-                 slabs (wgrad_pair: both nets per launch)
+                 dH1 as one batched bmm against the adjacent-W2 [2, H, H]
+                 view, split-K wgrads into per-chain slabs (wgrad_pair: both
+                 nets per launch); the layer-1 wgrad forms dZ1 = dH1 *
+                 silu'(Z1) in its staging (wgrad_pair_act; STOIX_FUSED_DZ1=0:
+                 one silu_bwd into dZ1, then the plain pair)
                  -> one GPU: slab_reduce_norm_pair (both chains' reduce +
                  squared norms) -> adam_pair (both chains' clip + Adam +
                  bf16 mirror), two launches
@@ -325,17 +331,25 @@ class FusedPPOEngine:
         z = lambda *s, dtype=torch.bfloat16: torch.zeros(*s, dtype=dtype, device=dev)
 
         class _Ws:
-            def __init__(ws):
-                ws.Xmb = z(S, self.K1P)  # K-padded GEMM input (zeros past OBS)
+            def __init__(ws, rows=S):
+                ws.Xmb = z(rows, self.K1P)  # K-padded GEMM input (zeros past OBS)
                 if self.discrete:
-                    ws.act = torch.zeros(S, dtype=torch.long, device=dev)
+                    ws.act = torch.zeros(rows, dtype=torch.long, device=dev)
                 else:
-                    ws.act = z(S, ACT, dtype=torch.float32)
-                ws.logp = z(S, dtype=torch.float32)
-                ws.val = z(S, dtype=torch.float32)
-                ws.adv = z(S, dtype=torch.float32)
-                ws.tgt = z(S, dtype=torch.float32)
+                    ws.act = z(rows, ACT, dtype=torch.float32)
+                ws.logp = z(rows, dtype=torch.float32)
+                ws.val = z(rows, dtype=torch.float32)
+                ws.adv = z(rows, dtype=torch.float32)
+                ws.tgt = z(rows, dtype=torch.float32)
 
+            def rows(ws, lo, hi):
+                """The same fields, rows [lo, hi) (views)."""
+                v = object.__new__(_Ws)
+                for k, t in vars(ws).items():
+                    setattr(v, k, t[lo:hi])
+                return v
+
+        self._Ws = _Ws
         self.ws = [_Ws(), _Ws()]
         # single-set aliases (perf probes / tests reach these)
         self.Xmb = self.ws[0].Xmb
@@ -397,6 +411,32 @@ class FusedPPOEngine:
         # concurrent gather steals bandwidth instead of hiding latency.
         # Kept behind a knob as a documented negative result.
         self.prefetch = _os.environ.get("STOIX_FUSED_PREFETCH", "0") == "1"
+        # STOIX_FUSED_DZ1: 1 (default) = the layer-1 wgrad forms
+        # dZ1 = dH1 * silu'(Z1) while it stages its tiles (wgrad_pair_act):
+        # no silu_bwd launch for layer 1 and dZ1 is neither written nor read.
+        # 0 = silu_bwd into dZ1, then the plain pair. Same slabs bit for bit.
+        # Needs the paired wgrad; where the launcher does not take the shape
+        # the knob-off launches run (dZ1 stays allocated for both cases).
+        self.fused_dz1 = _os.environ.get("STOIX_FUSED_DZ1", "1") != "0"
+        # STOIX_EPOCH_GATHER: 1 (default) = one ppo_gather_rows launch per
+        # epoch over the whole permutation into epoch-sized buffers (about
+        # 59 MB more at the flagship shape: n_mb * S rows of K1P bf16, ACT + 4
+        # floats); the minibatches read contiguous row slices of them. 0 =
+        # one ppo_gather per minibatch. Same rows bit for bit. The permutation
+        # and the gmean/gvar snapshot are fixed before an epoch starts, so
+        # nothing the gather reads changes during it. Only with S % 4 == 0
+        # (every slice base stays 16-byte aligned for the consumers' vector
+        # accesses), and not with the prefetch knob, which keeps its
+        # per-minibatch gather.
+        n_mb = int(sysc.num_minibatches)
+        self.epoch_gather = (
+            _os.environ.get("STOIX_EPOCH_GATHER", "1") != "0"
+            and S % 4 == 0 and not self.prefetch
+        )
+        if self.epoch_gather:
+            self.ws_epoch = _Ws(n_mb * S)
+            self.ws_mb = [self.ws_epoch.rows(mb * S, (mb + 1) * S)
+                          for mb in range(n_mb)]
 
         import torch.distributed as dist
 
@@ -651,6 +691,15 @@ class FusedPPOEngine:
                 gmean, gvar,
             )
 
+        # one gather for the whole epoch, first node of the epoch graph; a
+        # shape the kernel does not take leaves the per-minibatch gathers
+        we = self.ws_epoch if self.epoch_gather else None
+        epoch_rows = we is not None and ext.ppo_gather_rows(
+            L.perm_buf[: n_mb * S], flat_obs, flat_action, flat_logp,
+            flat_value, flat_adv, flat_tgt, we.Xmb, we.act, we.logp, we.val,
+            we.adv, we.tgt, gmean, gvar,
+        )
+
         # gather prefetch: minibatch mb+1's gather runs on a side stream
         # while mb's backward is on the main stream; double-buffered
         # workspaces + events make the dependency explicit (capture-legal:
@@ -667,10 +716,10 @@ class FusedPPOEngine:
         tail = self._tail_eligible()
         for mb in range(n_mb):
             p = mb & 1 if prefetch else 0
-            w = self.ws[p]
+            w = self.ws_mb[mb] if epoch_rows else self.ws[p]
             if prefetch:
                 cur.wait_event(self.ev_ready[p])
-            else:
+            elif not epoch_rows:
                 gather_into(mb, w)
             # ---- forward. Layer 1 (K=32): the custom fused Linear+SiLU
             # MFMA kernel wins (14.4 us vs 11.2 GEMM + silu pass). Layer 2
@@ -757,11 +806,17 @@ class FusedPPOEngine:
             else:
                 torch.mm(self.dZ2[0], a16["W2"], out=self.dH1[0])
                 torch.mm(self.dZ2[1], c16["W2"], out=self.dH1[1])
-            ext.silu_bwd(self.dH1, self.Z1, self.dZ1)
-            if pair:
+            if pair and self.fused_dz1 and ext.wgrad_pair_act(
+                self.dH1[0], self.Z1[0], w.Xmb, ac.slab, ao["W1"], ao["b1"], self.H,
+                self.dH1[1], self.Z1[1], w.Xmb, cc.slab, co["W1"], co["b1"], self.H,
+            ):
+                pass  # dZ1 formed inside the wgrad: no silu_bwd, no dZ1
+            elif pair:
+                ext.silu_bwd(self.dH1, self.Z1, self.dZ1)
                 ext.wgrad_pair(self.dZ1[0], w.Xmb, ac.slab, ao["W1"], ao["b1"], self.H,
                                self.dZ1[1], w.Xmb, cc.slab, co["W1"], co["b1"], self.H)
             else:
+                ext.silu_bwd(self.dH1, self.Z1, self.dZ1)
                 ext.wgrad(self.dZ1[0], w.Xmb, ac.slab, ao["W1"], ao["b1"], self.H)
                 ext.wgrad(self.dZ1[1], w.Xmb, cc.slab, co["W1"], co["b1"], self.H)
             if prefetch:

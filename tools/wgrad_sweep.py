@@ -4,7 +4,9 @@ Shapes (S=32768): W2 N=256 K=256; W1 N=256 K=32; Wh N=16 K=256; Wv N=1 K=256.
 
 --pair sweeps the pipelined, paired kernel (ext.wgrad_pair) instead: per
 flagship shape its tile / stage-depth variants against the two old launches
-it replaces, and the paired reduce against two slab_reduce calls. The
+it replaces, for layer 1 also the form with the SiLU backward in its staging
+(ext.wgrad_pair_act, two stage depths) against silu_bwd + the plain pair, and
+the paired reduce against two slab_reduce calls. The
 operands rotate through more than 256 MB per shape, so the Infinity Cache
 does not serve what the engine streams from HBM.
 """
@@ -135,6 +137,51 @@ def main_pair():
             print(f"  pair variant {v} ({desc}): {t:.2f} us, "
                   f"{need / t / 1e6:.2f} TB/s, "
                   f"{'bit-equal' if same else 'MISMATCH'}")
+        if name != "W1":
+            continue
+        # layer 1 with the SiLU backward inside the staging (wgrad_pair_act)
+        # against silu_bwd + the plain pair; dH and Z stacked [2, S, N] as in
+        # the engine, rotating like the sets above
+        stk = [(torch.randn(2, S, NS, device=dev, dtype=bf) * 0.1,
+                torch.randn(2, S, NS, device=dev, dtype=bf) * 3.0,
+                torch.randn(S, K, device=dev, dtype=bf)) for _ in range(nsets // 2 + 1)]
+        dZs = torch.zeros(2, S, NS, device=dev, dtype=bf)
+        jt = [0]
+
+        def nxt3():
+            jt[0] = (jt[0] + 1) % len(stk)
+            return stk[jt[0]]
+
+        def unfused():
+            dH, Z, X = nxt3()
+            ext.silu_bwd(dH, Z, dZs)
+            ext.wgrad_pair(dZs[0], X, slabs[0], off, off + NS * K, NS,
+                           dZs[1], X, slabs[1], off, off + NS * K, NS)
+
+        def fused(v):
+            dH, Z, X = nxt3()
+            assert ext.wgrad_pair_act(dH[0], Z[0], X, slabs[0], off, off + NS * K, NS,
+                                      dH[1], Z[1], X, slabs[1], off, off + NS * K, NS, v)
+
+        need = 2 * 2 * S * NS * 2 + S * K * 2 + 64 * 4 * 2 * (NS * K + NS)
+        print(f"  silu_bwd + pair: {timeit(unfused):.2f} us; fused needs "
+              f"{need / 1e6:.1f} MB = {need / 6.3e6:.2f} us at 6.3 TB/s")
+        for v, desc in ((0, "2 steps/stage"), (1, "1 step/stage")):
+            t = timeit(lambda: fused(v))
+            jt[0] = 0
+            unfused()
+            want = [s.clone() for s in slabs]
+            for s in slabs:
+                s.fill_(float("nan"))
+            jt[0] = 0
+            fused(v)
+            same = all(torch.equal(a.view(torch.int32)[:, off:off + NS * K + NS],
+                                   b.view(torch.int32)[:, off:off + NS * K + NS])
+                       for a, b in zip(slabs, want))
+            for s in slabs:
+                s.zero_()
+            print(f"  wgrad_pair_act variant {v} ({desc}): {t:.2f} us, "
+                  f"{need / t / 1e6:.2f} TB/s, {'bit-equal' if same else 'MISMATCH'}")
     grads = [torch.zeros(stride, device=dev, dtype=bf) for _ in range(2)]
     e0 = torch.zeros(0, device=dev)
     e1 = torch.zeros(0, dtype=torch.int64, device=dev)
