@@ -52,28 +52,31 @@ def _headers_digest() -> str:
 # not a timing choice, and nothing in the kernels relies on it.
 # cpp_extension.load() has one flag list for every source, and the older
 # files keep the code generation their committed measurements were taken
-# with, so this one object is compiled here and handed to the link.
-NOISY_SRC = CSRC / "noisy.hip"
-NOISY_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc",
-               "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# with, so such a file is compiled here, one object each, and handed to the
+# link.
+# qr.hip is a new kernel file too, so it goes the same way. (FMA contraction
+# is a pragma inside the files that need it off, not a flag here.)
+OWN_OBJECT_SOURCES = [CSRC / "noisy.hip", CSRC / "qr.hip"]
+OWN_OBJECT_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc",
+                    "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
-def _build_noisy_object(verbose: bool = False) -> Path:
-    """build/noisy_<digest>.o, the digest over the source, csrc/*.h and the
+def _build_own_object(src: Path, verbose: bool = False) -> Path:
+    """build/<stem>_<digest>.o, the digest over the source, csrc/*.h and the
     flags: a changed input gives a new name, and a new name on the link line
     makes ninja link again. Safe with several processes building at once:
     each compiles to a file of its own and renames it into place, and nothing
     is deleted (objects of older digests stay in the ignored build directory)."""
     from torch.utils.cpp_extension import ROCM_HOME
 
-    h = hashlib.sha1(NOISY_SRC.read_bytes())
+    h = hashlib.sha1(src.read_bytes())
     h.update(_headers_digest().encode())
-    h.update(" ".join(NOISY_FLAGS).encode())
-    obj = BUILD_DIR / f"noisy_{h.hexdigest()[:16]}.o"
+    h.update(" ".join(OWN_OBJECT_FLAGS).encode())
+    obj = BUILD_DIR / f"{src.stem}_{h.hexdigest()[:16]}.o"
     if not obj.exists():
         tmp = BUILD_DIR / f"tmp{os.getpid()}_{obj.name}"
-        cmd = [str(Path(ROCM_HOME) / "bin" / "hipcc"), *NOISY_FLAGS, "-I", str(CSRC),
-               "-c", str(NOISY_SRC), "-o", str(tmp)]
+        cmd = [str(Path(ROCM_HOME) / "bin" / "hipcc"), *OWN_OBJECT_FLAGS, "-I", str(CSRC),
+               "-c", str(src), "-o", str(tmp)]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
@@ -88,7 +91,7 @@ def build(verbose: bool = False):
     from torch.utils.cpp_extension import load
 
     BUILD_DIR.mkdir(exist_ok=True)
-    noisy_obj = _build_noisy_object(verbose)
+    own_objects = [str(_build_own_object(src, verbose)) for src in OWN_OBJECT_SOURCES]
     sources = [s for s in SOURCES if os.path.exists(s)]
     mod = load(
         name="stoix_amd_C",
@@ -96,7 +99,7 @@ def build(verbose: bool = False):
         extra_cflags=["-O3", "-std=c++17"],
         extra_cuda_cflags=["-O3", "-std=c++17", "--offload-arch=gfx950",
                            f"-DSTOIX_CSRC_HEADERS=0x{_headers_digest()}"],
-        extra_ldflags=[str(noisy_obj)],
+        extra_ldflags=own_objects,
         build_directory=str(BUILD_DIR),
         verbose=verbose,
         with_cuda=True,

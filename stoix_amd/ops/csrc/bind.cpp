@@ -967,6 +967,103 @@ void c51_loss_bwd(torch::Tensor grad_ce, torch::Tensor logits_tm1,
                       cur_stream());
 }
 
+// Argument checks shared by the two QR loss launchers (qr.hip): quantile
+// tensors are contiguous fp32 or bf16 [B, quantiles, A], action innermost,
+// with 1 <= A <= 64 and 1 <= quantiles <= 1024; the per-row vectors follow
+// check_c51_vector. Returns 1 for bf16.
+int check_qr_dist(const torch::Tensor& t, const char* name, int64_t B,
+                  int64_t A) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name,
+              " must be a contiguous GPU tensor");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 ||
+                  t.scalar_type() == torch::kBFloat16,
+              name, " must be fp32 or bf16");
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == B && t.size(2) == A, name,
+              " must be [", B, ", quantiles, ", A, "]");
+  TORCH_CHECK(A >= 1 && A <= 64, "qr loss supports 1 <= A <= 64, got ", A);
+  TORCH_CHECK(t.size(1) >= 1 && t.size(1) <= 1024,
+              "qr loss supports 1 <= quantiles <= 1024, got ", t.size(1));
+  return t.scalar_type() == torch::kBFloat16 ? 1 : 0;
+}
+
+const long* check_qr_actions(const torch::Tensor& a_tm1, int64_t B,
+                             int64_t A) {
+  if (a_tm1.numel() == 0) {
+    TORCH_CHECK(A == 1, "qr loss: an empty a_tm1 needs A == 1, got ", A);
+    return nullptr;
+  }
+  check_c51_vector(a_tm1, "a_tm1", torch::kInt64, B);
+  return a_tm1.data_ptr<long>();
+}
+
+void qr_loss_fwd(torch::Tensor src, torch::Tensor tau, torch::Tensor a_tm1,
+                 torch::Tensor r_t, torch::Tensor d_t, torch::Tensor sel,
+                 torch::Tensor tgt, torch::Tensor loss, torch::Tensor gth,
+                 double huber_param) {
+  TORCH_CHECK(src.dim() == 3, "src must be [B, N, A]");
+  const int64_t B = src.size(0), N = src.size(1), A = src.size(2);
+  const int src_bf16 = check_qr_dist(src, "src", B, A);
+  const int tgt_bf16 = check_qr_dist(tgt, "tgt", B, A);
+  const int64_t M = tgt.size(1);
+  // tau: [N], or [B, N] rows of unit element stride (row stride 0 for an
+  // expanded view)
+  TORCH_CHECK(tau.is_cuda() && tau.scalar_type() == torch::kFloat32 &&
+                  (tau.dim() == 1 || tau.dim() == 2) && tau.size(-1) == N &&
+                  (N == 1 || tau.stride(-1) == 1),
+              "tau must be fp32 [N] or [B, N] with contiguous rows");
+  int64_t tau_stride = 0;
+  if (tau.dim() == 2) {
+    TORCH_CHECK(tau.size(0) == B && tau.stride(0) >= 0,
+                "tau must be [", B, ", ", N, "] with a non-negative row stride");
+    tau_stride = tau.stride(0);
+  }
+  const long* ap = check_qr_actions(a_tm1, B, A);
+  const float *rp = nullptr, *dp = nullptr;
+  TORCH_CHECK((r_t.numel() == 0) == (d_t.numel() == 0) || B == 0,
+              "qr loss: r_t and d_t come together");
+  if (r_t.numel() > 0) {
+    check_c51_vector(r_t, "r_t", torch::kFloat32, B);
+    check_c51_vector(d_t, "d_t", torch::kFloat32, B);
+    rp = r_t.data_ptr<float>();
+    dp = d_t.data_ptr<float>();
+  }
+  const void* sp = nullptr;
+  int sel_bf16 = 0;
+  int64_t Ns = 1;
+  if (sel.numel() > 0) {
+    sel_bf16 = check_qr_dist(sel, "sel", B, A);
+    Ns = sel.size(1);
+    sp = sel.data_ptr();
+  } else {
+    TORCH_CHECK(A == 1, "qr loss: an empty selector needs A == 1, got ", A);
+  }
+  check_c51_rows(loss, "loss", B, 1);
+  check_c51_rows(gth, "gth", B, N);
+  const int rc = launch_qr_loss_fwd(
+      src.data_ptr(), tau.data_ptr<float>(), ap, rp, dp, sp, tgt.data_ptr(),
+      loss.data_ptr<float>(), gth.data_ptr<float>(), (int)B, (int)A, (int)N,
+      (int)M, (int)Ns, src_bf16, tgt_bf16, sel_bf16, (float)huber_param,
+      (long)tau_stride, ap ? (long)a_tm1.stride(0) : 0,
+      rp ? (long)r_t.stride(0) : 0, dp ? (long)d_t.stride(0) : 0,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "qr_loss_fwd: sizes outside the kernel's range");
+}
+
+void qr_loss_bwd(torch::Tensor grad, torch::Tensor gth, torch::Tensor a_tm1,
+                 torch::Tensor dsrc) {
+  TORCH_CHECK(dsrc.dim() == 3, "dsrc must be [B, N, A]");
+  const int64_t B = dsrc.size(0), N = dsrc.size(1), A = dsrc.size(2);
+  const int is_bf16 = check_qr_dist(dsrc, "dsrc", B, A);
+  const long* ap = check_qr_actions(a_tm1, B, A);
+  check_c51_rows(gth, "gth", B, N);
+  check_c51_vector(grad, "grad", torch::kFloat32, B);
+  const int rc = launch_qr_loss_bwd(
+      grad.data_ptr<float>(), (long)grad.stride(0), gth.data_ptr<float>(), ap,
+      ap ? (long)a_tm1.stride(0) : 0, dsrc.data_ptr(), (int)B, (int)N, (int)A,
+      is_bf16, cur_stream());
+  TORCH_CHECK(rc == 0, "qr_loss_bwd: sizes outside the kernel's range");
+}
+
 // Argument checks shared by the NoisyLinear launchers (noisy.hip): the fp32
 // parameters mu_w / sigma_w [N, K] contiguous and 16-byte aligned, the noise
 // vectors fp32 views of the NoiseBank buffer (any offset, unit stride), and
@@ -1388,6 +1485,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "C51 categorical TD loss: softmax + fixed-order projection + CE");
   m.def("c51_loss_bwd", &c51_loss_bwd,
         "C51 categorical TD loss: analytic logits backward");
+  m.def("qr_loss_fwd", &qr_loss_fwd,
+        "QR-DQN quantile loss: selector argmax + target + all pairs, one "
+        "pass giving the per-row loss and d loss / d source quantile");
+  m.def("qr_loss_bwd", &qr_loss_bwd,
+        "QR-DQN quantile loss: scatter of the saved gradient to [B, N, A]");
   m.def("noisy_linear_fwd", &noisy_linear_fwd,
         "NoisyLinear forward, the noisy weight formed while staging");
   m.def("noisy_linear_dgrad", &noisy_linear_dgrad,

@@ -271,6 +271,21 @@ void launch_c51_loss_bwd(const float* grad_ce, long grad_stride,
                          int B, int A, int M, int is_bf16, long a_stride,
                          void* stream);
 
+// ---- qr.hip. Null a_tm1 / sel: A == 1; null r_t and d_t together: the
+// target samples are read as they are. tau_stride is the row stride of tau
+// (0: one [N] for every row). Both return 0 after the launch, 1 for sizes
+// the kernels do not take (1 <= N, M, Ns <= 1024, 1 <= A <= 64), launching
+// nothing.
+int launch_qr_loss_fwd(
+    const void* src, const float* tau, const long* a_tm1, const float* r_t,
+    const float* d_t, const void* sel, const void* tgt, float* loss,
+    float* gth, int B, int A, int N, int M, int Ns, int src_bf16,
+    int tgt_bf16, int sel_bf16, float huber_param, long tau_stride,
+    long a_stride, long r_stride, long d_stride, void* stream);
+int launch_qr_loss_bwd(const float* grad, long grad_stride, const float* gth,
+                       const long* a_tm1, long a_stride, void* dsrc, int B,
+                       int N, int A, int is_bf16, void* stream);
+
 // ---- mcts.hip
 void launch_mcts_select(
     const float* visit, const float* value_sum, const float* reward,

@@ -10,7 +10,9 @@ quantile_regression_loss / quantile_q_learning :226-314.
 All are written against batched torch tensors; each is differentiable so the
 update path can run under autograd (captured in a hip graph); the fused HIP
 loss+grad kernels used by the Anakin fast path are numerics-tested against
-these references (tests/test_losses.py).
+these references (tests/test_losses.py). On the GPU the distributional
+losses run in HIP: the categorical ones in c51.hip, the quantile ones in
+qr.hip (quantile_q_learning_rows is the per-row entry point).
 """
 from __future__ import annotations
 
@@ -508,6 +510,142 @@ def munchausen_q_learning(
     return _huber(target - q_a, huber_loss_parameter).mean()
 
 
+# -------------------------------------------------- fused QR loss (qr.hip)
+
+_QR_MAX_QUANTILES = 1024
+_QR_MAX_ACTIONS = 64
+
+
+def qr_fused_enabled() -> bool:
+    """STOIX_FUSED_QR=0 forces the torch composition (A/B timing)."""
+    return os.environ.get("STOIX_FUSED_QR", "1") != "0"
+
+
+def _qr_route_to_kernel(src, tau, tgt, sel=None, rows=()) -> bool:
+    """Whether a quantile loss below hands its inputs to the HIP kernels:
+    knob on, [B, quantiles, A] fp32/bf16 GPU tensors within the kernels' size
+    limits, tau [N] or [B, N] that needs no gradient, per-row vectors [B]."""
+    if not qr_fused_enabled() or not isinstance(src, Tensor) or src.dim() != 3:
+        return False
+    B, N, A = src.shape
+    for t in (src, tgt) if sel is None else (src, tgt, sel):
+        if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):
+            return False
+        if t.dim() != 3 or t.shape[0] != B or t.shape[2] != A:
+            return False
+        if not 1 <= t.shape[1] <= _QR_MAX_QUANTILES:
+            return False
+    if B < 1 or not 1 <= A <= _QR_MAX_ACTIONS:
+        return False
+    if not tau.is_cuda or not tau.is_floating_point() or tau.shape not in ((N,), (B, N)):
+        return False
+    if tau.requires_grad and torch.is_grad_enabled():
+        return False
+    return all(isinstance(v, Tensor) and v.is_cuda and v.shape == (B,) for v in rows)
+
+
+class _QRLoss(torch.autograd.Function):
+    """Per-row quantile-regression loss with its closed-form gradient to the
+    source quantiles, GPU only: forward is qr_loss_fwd (which also leaves
+    d loss / d th in ``gth [B, N]``), backward is qr_loss_bwd. Nothing flows
+    to tau, the target samples, the selector, r or d.
+
+    ``src [B, N, A]``, ``tgt [B, M, A]``, ``sel [B, Ns, A]`` or None (A = 1),
+    ``a`` int [B] or None (A = 1), ``r``/``d`` [B] or both None (targets taken
+    as they are)."""
+
+    @staticmethod
+    def forward(ctx, src, tau, a, r, d, sel, tgt, huber_param):
+        from stoix_amd.ops import ext
+
+        B, N, A = src.shape
+        src = src.contiguous()
+        dev = src.device
+        empty = torch.empty(0, dtype=torch.float32, device=dev)
+        tau = tau.float()
+        if N > 1 and tau.stride(-1) != 1:
+            tau = tau.contiguous()
+        a_arg = torch.empty(0, dtype=torch.long, device=dev) if a is None else a.long()
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        gth = torch.empty(B, N, dtype=torch.float32, device=dev)
+        ext(required=True).qr_loss_fwd(
+            src,
+            tau,  # [N], or [B, N] read through its row stride
+            a_arg,  # per-row vectors may be strided views
+            empty if r is None else r.float(),
+            empty if d is None else d.float(),
+            empty if sel is None else sel.contiguous(),
+            tgt.contiguous(),
+            loss,
+            gth,
+            float(huber_param),
+        )
+        ctx.save_for_backward(gth, a_arg)
+        ctx.src_meta = (src.shape, src.dtype)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        from stoix_amd.ops import ext
+
+        gth, a_arg = ctx.saved_tensors
+        shape, dtype = ctx.src_meta
+        dsrc = torch.empty(shape, dtype=dtype, device=gth.device)
+        ext(required=True).qr_loss_bwd(grad_loss.float(), gth, a_arg, dsrc)
+        return dsrc, None, None, None, None, None, None, None
+
+
+def _qr_rows_composition(dist_src, tau_src, dist_target, huber_param) -> Tensor:
+    """Per-row loss [B] from the torch ops quantile_regression_loss is made
+    of (its lines without the final mean)."""
+    if tau_src.dim() == 1:
+        tau_src = tau_src.unsqueeze(0).expand(dist_src.shape[0], -1)
+    delta = dist_target.detach().unsqueeze(1) - dist_src.unsqueeze(2)
+    weight = (tau_src.unsqueeze(2) - (delta < 0).to(delta.dtype)).abs()
+    if huber_param > 0:
+        loss = _huber(delta, huber_param) / huber_param
+    else:
+        loss = delta.abs()
+    return (weight * loss).mean(dim=2).sum(dim=1)
+
+
+def quantile_q_learning_rows(
+    dist_q_tm1: Tensor,
+    tau_q_tm1: Tensor,
+    a_tm1: Tensor,
+    r_t: Tensor,
+    d_t: Tensor,
+    dist_q_t_selector: Tensor,
+    dist_q_t: Tensor,
+    huber_param: float = 1.0,
+) -> Tensor:
+    """Per-row QR-DQN loss ``[B]``; ``quantile_q_learning`` is its mean. For
+    callers that weight the rows (importance weights, priorities).
+
+    dist_q [B, quantiles, A], tau [N] or [B, N], a/r/d [B]. On the GPU,
+    fp32/bf16 inputs with at most 1024 quantiles and 64 actions run in the
+    two qr.hip kernels (fp32 rows; the gradient in dist_q_tm1's dtype, summed
+    in a fixed order, so the same bits on every run). Anything else, or
+    STOIX_FUSED_QR=0, runs the torch composition.
+    """
+    if _qr_route_to_kernel(
+        dist_q_tm1, tau_q_tm1, dist_q_t, dist_q_t_selector, (a_tm1, r_t, d_t)
+    ):
+        return _QRLoss.apply(
+            dist_q_tm1, tau_q_tm1, a_tm1, r_t, d_t, dist_q_t_selector, dist_q_t, huber_param
+        )
+    q_a = dist_q_tm1.gather(
+        2, a_tm1.long().view(-1, 1, 1).expand(-1, dist_q_tm1.shape[1], 1)
+    ).squeeze(-1)
+    best_a = dist_q_t_selector.mean(dim=1).argmax(dim=-1)
+    target_dist = dist_q_t.gather(
+        2, best_a.view(-1, 1, 1).expand(-1, dist_q_t.shape[1], 1)
+    ).squeeze(-1)
+    target = (r_t.unsqueeze(-1) + d_t.unsqueeze(-1) * target_dist).detach()
+    return _qr_rows_composition(q_a, tau_q_tm1, target, huber_param)
+
+
 def quantile_regression_loss(
     dist_src: Tensor,
     tau_src: Tensor,
@@ -518,7 +656,19 @@ def quantile_regression_loss(
 
     dist_src [B, N] quantile estimates with thresholds tau_src [N] (or [B, N]);
     dist_target [B, M] target samples.
+
+    On the GPU, eligible inputs run in the fused qr.hip kernels (as A = 1,
+    see quantile_q_learning_rows).
     """
+    if (
+        dist_src.dim() == 2
+        and dist_target.dim() == 2
+        and _qr_route_to_kernel(dist_src.unsqueeze(-1), tau_src, dist_target.unsqueeze(-1))
+    ):
+        return _QRLoss.apply(
+            dist_src.unsqueeze(-1), tau_src, None, None, None, None,
+            dist_target.detach().unsqueeze(-1), huber_param,
+        ).mean()
     if tau_src.dim() == 1:
         tau_src = tau_src.unsqueeze(0).expand(dist_src.shape[0], -1)
     # pairwise TD errors: target_j - src_i -> [B, N, M]
@@ -545,7 +695,16 @@ def quantile_q_learning(
 
     dist_q [B, N, A]; selector distribution picks argmax over mean-quantile
     values; target dist = r + d * dist_q_t[:, :, a*].
+
+    On the GPU, eligible inputs run in the fused qr.hip kernels
+    (quantile_q_learning_rows).
     """
+    if _qr_route_to_kernel(
+        dist_q_tm1, tau_q_tm1, dist_q_t, dist_q_t_selector, (a_tm1, r_t, d_t)
+    ):
+        return _QRLoss.apply(
+            dist_q_tm1, tau_q_tm1, a_tm1, r_t, d_t, dist_q_t_selector, dist_q_t, huber_param
+        ).mean()
     q_a = dist_q_tm1.gather(
         2, a_tm1.long().view(-1, 1, 1).expand(-1, dist_q_tm1.shape[1], 1)
     ).squeeze(-1)

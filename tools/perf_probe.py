@@ -4,6 +4,9 @@ Run on a GPU box:  python tools/perf_probe.py
 Prints: fused-engine attach status, rollout vs epoch wall times (graphed and
 eager), and microbenchmarks of the individual fused kernels.
 `python tools/perf_probe.py c51` runs only the C51 loss microbenchmark.
+`python tools/perf_probe.py qr` runs only the QR loss microbenchmark, and
+`python tools/perf_probe.py qr-sps` ff_qr_dqn steps per second with and
+without the fused QR loss, one fresh process per run.
 """
 from __future__ import annotations
 
@@ -75,6 +78,90 @@ def c51_loss_probe():
             graphed = timeit(graph.replay, 200, 10) * 1e3
             print(f"c51 loss fwd+bwd B={B:5d} {name}: eager {eager:8.1f} us"
                   f"  graphed {graphed:8.1f} us")
+
+
+def _eager_and_graphed_us(fn):
+    """(eager, graph-replayed) microseconds of one call of ``fn``."""
+    eager = timeit(fn, 200, 10) * 1e3
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fn()
+    return eager, timeit(graph.replay, 200, 10) * 1e3
+
+
+def qr_loss_probe():
+    """QR-DQN loss forward + backward, fp32, at the ff_qr_dqn default (A = 2,
+    51 quantiles) and the quantile head's default (200 quantiles, A = 4):
+    the qr.hip kernels vs the torch chain (STOIX_FUSED_QR=0) in the same
+    process; eager, and replayed from a hip graph as the update runs it."""
+    from stoix_amd.ops import losses
+
+    dev = torch.device("cuda:0")
+    for B in (512, 4096):
+        for A, N in ((2, 51), (4, 200)):
+            g = torch.Generator(device=dev).manual_seed(B + N)
+            src = (2 * torch.randn(B, N, A, device=dev, generator=g)).requires_grad_(True)
+            tgt = 2 * torch.randn(B, N, A, device=dev, generator=g)
+            sel = torch.randn(B, N, A, device=dev, generator=g)
+            tau = (torch.arange(N, device=dev, dtype=torch.float32) + 0.5) / N
+            a = torch.randint(0, A, (B,), device=dev, generator=g)
+            r = torch.randn(B, device=dev, generator=g)
+            d = 0.99 * (torch.rand(B, device=dev, generator=g) < 0.9).float()
+
+            def step():
+                loss = losses.quantile_q_learning(src, tau, a, r, d, sel, tgt, 1.0)
+                return torch.autograd.grad(loss, src)[0]
+
+            for name, knob in (("fused", "1"), ("torch", "0"), ("fused", "1"), ("torch", "0")):
+                os.environ["STOIX_FUSED_QR"] = knob
+                eager, graphed = _eager_and_graphed_us(step)
+                print(f"qr loss fwd+bwd B={B:5d} A={A} N={N:3d} {name}: eager {eager:8.1f} us"
+                      f"  graphed {graphed:8.1f} us", flush=True)
+    os.environ.pop("STOIX_FUSED_QR", None)
+
+
+def qr_sps_child(num_envs, updates):
+    """ff_qr_dqn at its default composition (CartPole), update graph captured
+    as run_anakin_experiment does: env steps per second over ``updates``."""
+    import json
+
+    from stoix_amd import envs as environments
+    from stoix_amd.config import compose
+    from stoix_amd.ops.graph import try_enable_update_graph
+    from stoix_amd.systems.q_learning.ff_qr_dqn import learner_factory
+    from stoix_amd.utils.total_timestep_checker import check_total_timesteps
+
+    cfg = compose("default/anakin/default_ff_qr_dqn.yaml",
+                  [f"arch.total_num_envs={num_envs}", "arch.total_timesteps=null",
+                   f"arch.num_updates={updates}", "arch.num_evaluation=1", "logger.loggers=[]"])
+    cfg.arch.n_devices = 1
+    check_total_timesteps(cfg)
+    device = torch.device("cuda:0")
+    torch.manual_seed(int(cfg.arch.seed))
+    env = environments.make_single(cfg, num_envs, device, seed=int(cfg.arch.seed))
+    learner = learner_factory(cfg, env, device)
+    graphed = try_enable_update_graph(learner)
+    ms = timeit(learner.update_step, iters=updates, warmup=5)
+    steps = int(cfg.system.rollout_length) * num_envs
+    print(json.dumps({"system": "ff_qr_dqn", "fused": os.environ.get("STOIX_FUSED_QR", "1") != "0",
+                      "num_envs": num_envs, "graphed": graphed, "updates": updates,
+                      "ms_per_update": round(ms, 4), "sps": round(steps / ms * 1e3)}), flush=True)
+
+
+def qr_sps_probe(updates=200):
+    """Fresh child process per run, fused and torch alternating, twice each."""
+    import subprocess
+
+    for num_envs in (1024, 4096):
+        for knob in ("1", "0", "1", "0"):
+            subprocess.run([sys.executable, os.path.abspath(__file__), "_qr_sps_child",
+                            str(num_envs), str(updates)],
+                           env=dict(os.environ, STOIX_FUSED_QR=knob), check=True, timeout=300)
 
 
 def main():
@@ -274,6 +361,13 @@ def main():
 
 
 if __name__ == "__main__":
-    if "c51" not in sys.argv[1:]:
-        main()
-    c51_loss_probe()
+    if sys.argv[1:2] == ["qr"]:
+        qr_loss_probe()
+    elif sys.argv[1:2] == ["qr-sps"]:
+        qr_sps_probe()
+    elif sys.argv[1:2] == ["_qr_sps_child"]:
+        qr_sps_child(int(sys.argv[2]), int(sys.argv[3]))
+    else:
+        if "c51" not in sys.argv[1:]:
+            main()
+        c51_loss_probe()
