@@ -16,6 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 Tensor = torch.Tensor
 
@@ -142,6 +143,55 @@ class MultivariateNormalDiag(Distribution):
         return self._n.loc
 
 
+class _TanhNormalRsample(torch.autograd.Function):
+    """``(a, logp)`` of a reparameterised tanh-Normal sample from the noise
+    ``eps``, GPU only: forward is tanh_normal_rsample_fwd (which keeps
+    ``tanh(u)`` when a gradient is needed), backward the closed form of
+    tanh_normal_rsample_bwd to loc and scale. Leading dims are flattened to
+    rows; ``a`` comes in loc's dtype, ``logp`` in fp32. ``keep`` false (the
+    caller is under no_grad or nothing requires a gradient; ``needs_input_grad``
+    does not know the grad mode) leaves ``tanh(u)`` unallocated and unwritten."""
+
+    @staticmethod
+    def forward(ctx, loc, scale, eps, scale_affine, shift_affine, keep):
+        from stoix_amd.ops import ext
+
+        A = loc.shape[-1]
+        loc2, scale2 = loc.reshape(-1, A).contiguous(), scale.reshape(-1, A).contiguous()
+        eps2 = eps.reshape(-1, A).contiguous()
+        B = loc2.shape[0]
+        a = torch.empty_like(loc2)
+        logp = torch.empty(B, dtype=torch.float32, device=loc.device)
+        t = torch.empty((B, A) if keep else (0,), dtype=torch.float32, device=loc.device)
+        ext(required=True).tanh_normal_rsample_fwd(
+            loc2, scale2, eps2, a, logp, t, scale_affine, shift_affine
+        )
+        if keep:
+            ctx.save_for_backward(t, eps2, scale2)
+            ctx.scale_affine = scale_affine
+            ctx.loc_dtype = loc.dtype
+        return a.view(loc.shape), logp.view(loc.shape[:-1])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, da, dlogp):
+        from stoix_amd.ops import ext
+
+        t, eps2, scale2 = ctx.saved_tensors
+        B, A = t.shape
+        dloc = torch.empty(B, A, dtype=ctx.loc_dtype, device=t.device)
+        dscale = torch.empty_like(scale2)
+        dlogp = dlogp.float()
+        if dlogp.dim() != 1:  # leading dims: one row vector, as the forward's rows
+            dlogp = dlogp.reshape(B)
+        ext(required=True).tanh_normal_rsample_bwd(
+            da.reshape(B, A).contiguous(), dlogp, t, eps2, scale2, dloc, dscale,
+            ctx.scale_affine,
+        )
+        shape = da.shape
+        return dloc.view(shape), dscale.view(shape), None, None, None, None
+
+
 class AffineTanhTransformedDistribution(Distribution):
     """tanh-squashed Gaussian affinely mapped to [minimum, maximum], with the
     boundary log-prob clipped for numerical stability (reference
@@ -185,7 +235,37 @@ class AffineTanhTransformedDistribution(Distribution):
     def rsample(self, generator=None) -> Tensor:
         return self._forward(self.base.rsample(generator))
 
+    def _route_to_kernel(self) -> bool:
+        """Whether sample_and_log_prob runs in the tanh_normal.hip kernels:
+        fp32/bf16 loc and scale of one shape on the GPU, Python-float bounds,
+        at most 64 action dimensions, STOIX_FUSED_SAC not 0."""
+        from stoix_amd.ops.losses import sac_fused_enabled
+
+        loc, scale = self.base.loc, self.base.scale
+        ok = (torch.float32, torch.bfloat16)
+        return (
+            isinstance(self.scale_affine, float)
+            and self.scale_affine > 0.0
+            and loc.is_cuda
+            and scale.is_cuda
+            and loc.dtype in ok
+            and scale.dtype in ok
+            and loc.dim() >= 1
+            and loc.shape == scale.shape
+            and 1 <= loc.shape[-1] <= 64
+            and loc.numel() > 0
+            and sac_fused_enabled()
+        )
+
     def sample_and_log_prob(self, generator=None) -> Tuple[Tensor, Tensor]:
+        if self._route_to_kernel():
+            loc = self.base.loc
+            # the draw Normal.rsample makes: same shape, dtype and generator
+            eps = torch.randn(loc.shape, device=loc.device, generator=generator)
+            keep = torch.is_grad_enabled() and (loc.requires_grad or self.base.scale.requires_grad)
+            return _TanhNormalRsample.apply(
+                loc, self.base.scale, eps, self.scale_affine, self.shift_affine, keep
+            )
         u = self.base.rsample(generator)
         a = self._forward(u)
         lp = self._log_prob_from_u(u)

@@ -1064,6 +1064,173 @@ void qr_loss_bwd(torch::Tensor grad, torch::Tensor gth, torch::Tensor a_tm1,
   TORCH_CHECK(rc == 0, "qr_loss_bwd: sizes outside the kernel's range");
 }
 
+// Argument checks of the tanh-Normal launchers (tanh_normal.hip): [B, A]
+// contiguous fp32 or bf16 (or exactly `ty` when given). Returns 1 for bf16.
+int check_tn_rows(const torch::Tensor& t, const char* name, int64_t B,
+                  int64_t A, c10::optional<torch::ScalarType> ty = c10::nullopt) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 &&
+                  t.size(0) == B && t.size(1) == A,
+              name, " must be a contiguous GPU tensor [", B, ", ", A, "]");
+  TORCH_CHECK(ty ? t.scalar_type() == *ty
+                 : (t.scalar_type() == torch::kFloat32 ||
+                    t.scalar_type() == torch::kBFloat16),
+              name, " has the wrong dtype");
+  return t.scalar_type() == torch::kBFloat16 ? 1 : 0;
+}
+
+void tanh_normal_rsample_fwd(torch::Tensor loc, torch::Tensor scale,
+                             torch::Tensor eps, torch::Tensor a,
+                             torch::Tensor logp, torch::Tensor t,
+                             double scale_affine, double shift_affine) {
+  TORCH_CHECK(loc.dim() == 2, "loc must be [B, A]");
+  const int64_t B = loc.size(0), A = loc.size(1);
+  TORCH_CHECK(B < (int64_t(1) << 31) - 256, "tanh_normal: too many rows");
+  const int loc_bf16 = check_tn_rows(loc, "loc", B, A);
+  const int scale_bf16 = check_tn_rows(scale, "scale", B, A);
+  check_tn_rows(eps, "eps", B, A, torch::kFloat32);
+  check_tn_rows(a, "a", B, A, loc.scalar_type());
+  check_c51_rows(logp, "logp", B, 1);
+  if (t.numel() > 0) check_tn_rows(t, "t", B, A, torch::kFloat32);  // else unsaved
+  const int rc = launch_tanh_normal_rsample_fwd(
+      loc.data_ptr(), scale.data_ptr(), eps.data_ptr<float>(), a.data_ptr(),
+      logp.data_ptr<float>(), fptr_or_null(t), (int)B, (int)A, loc_bf16,
+      scale_bf16, (float)scale_affine, (float)shift_affine, cur_stream());
+  TORCH_CHECK(rc == 0, "tanh_normal_rsample_fwd: needs 1 <= A <= 64 and a "
+                       "positive scale_affine");
+}
+
+void tanh_normal_rsample_bwd(torch::Tensor da, torch::Tensor dlogp,
+                             torch::Tensor t, torch::Tensor eps,
+                             torch::Tensor scale, torch::Tensor dloc,
+                             torch::Tensor dscale, double scale_affine) {
+  TORCH_CHECK(dloc.dim() == 2, "dloc must be [B, A]");
+  const int64_t B = dloc.size(0), A = dloc.size(1);
+  TORCH_CHECK(B < (int64_t(1) << 31) - 256, "tanh_normal: too many rows");
+  const int loc_bf16 = check_tn_rows(dloc, "dloc", B, A);
+  const int scale_bf16 = check_tn_rows(scale, "scale", B, A);
+  check_tn_rows(da, "da", B, A, dloc.scalar_type());
+  check_tn_rows(dscale, "dscale", B, A, scale.scalar_type());
+  check_tn_rows(t, "t", B, A, torch::kFloat32);
+  check_tn_rows(eps, "eps", B, A, torch::kFloat32);
+  check_c51_vector(dlogp, "dlogp", torch::kFloat32, B);
+  const int rc = launch_tanh_normal_rsample_bwd(
+      da.data_ptr(), dlogp.data_ptr<float>(), (long)dlogp.stride(0),
+      t.data_ptr<float>(), eps.data_ptr<float>(), scale.data_ptr(),
+      dloc.data_ptr(), dscale.data_ptr(), (int)B, (int)A, loc_bf16, scale_bf16,
+      (float)scale_affine, cur_stream());
+  TORCH_CHECK(rc == 0, "tanh_normal_rsample_bwd: needs 1 <= A <= 64");
+}
+
+// SAC row kernels (tanh_normal.hip): critic values are contiguous fp32
+// [Q, B] with 1 <= Q <= 4, log_alpha one fp32 value on the GPU.
+void check_sac_q(const torch::Tensor& t, const char* name, int64_t Q,
+                 int64_t B) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32 && t.dim() == 2 &&
+                  t.size(0) == Q && t.size(1) == B,
+              name, " must be a contiguous fp32 GPU tensor [", Q, ", ", B, "]");
+  TORCH_CHECK(Q >= 1 && Q <= 4, "sac rows support 1 <= Q <= 4, got ", Q);
+  TORCH_CHECK(B < (int64_t(1) << 31) - 256, "sac rows: too many rows");
+}
+
+const float* check_sac_log_alpha(const torch::Tensor& t) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                  t.numel() == 1,
+              "log_alpha must be one fp32 value on the GPU");
+  return t.data_ptr<float>();
+}
+
+void sac_critic_rows(torch::Tensor q_pred, torch::Tensor q_next,
+                     torch::Tensor logp_next, torch::Tensor r_t,
+                     torch::Tensor d_t, torch::Tensor log_alpha, double gamma,
+                     torch::Tensor target, torch::Tensor rows,
+                     torch::Tensor dq) {
+  TORCH_CHECK(q_pred.dim() == 2, "q_pred must be [Q, B]");
+  const int64_t Q = q_pred.size(0), B = q_pred.size(1);
+  check_sac_q(q_pred, "q_pred", Q, B);
+  check_sac_q(q_next, "q_next", Q, B);
+  check_sac_q(dq, "dq", Q, B);
+  check_c51_vector(logp_next, "logp_next", torch::kFloat32, B);
+  check_c51_vector(r_t, "r_t", torch::kFloat32, B);
+  check_c51_vector(d_t, "d_t", torch::kFloat32, B);
+  check_c51_rows(target, "target", B, 1);
+  check_c51_rows(rows, "rows", B, 1);
+  const int rc = launch_sac_critic_rows(
+      q_pred.data_ptr<float>(), q_next.data_ptr<float>(),
+      logp_next.data_ptr<float>(), (long)logp_next.stride(0),
+      r_t.data_ptr<float>(), (long)r_t.stride(0), d_t.data_ptr<float>(),
+      (long)d_t.stride(0), check_sac_log_alpha(log_alpha), (float)gamma,
+      target.data_ptr<float>(), rows.data_ptr<float>(), dq.data_ptr<float>(),
+      (int)Q, (int)B, cur_stream());
+  TORCH_CHECK(rc == 0, "sac_critic_rows: sizes outside the kernel's range");
+}
+
+void sac_actor_rows(torch::Tensor q_new, torch::Tensor logp_new,
+                    torch::Tensor log_alpha, double target_entropy,
+                    torch::Tensor actor_rows, torch::Tensor alpha_rows,
+                    torch::Tensor argmin, torch::Tensor entropy_rows) {
+  TORCH_CHECK(q_new.dim() == 2, "q_new must be [Q, B]");
+  const int64_t Q = q_new.size(0), B = q_new.size(1);
+  check_sac_q(q_new, "q_new", Q, B);
+  check_c51_vector(logp_new, "logp_new", torch::kFloat32, B);
+  check_c51_rows(actor_rows, "actor_rows", B, 1);
+  check_c51_rows(alpha_rows, "alpha_rows", B, 1);
+  check_c51_rows(entropy_rows, "entropy_rows", B, 1);
+  TORCH_CHECK(argmin.is_cuda() && argmin.is_contiguous() &&
+                  argmin.scalar_type() == torch::kInt32 && argmin.numel() == B,
+              "argmin must be a contiguous int32 GPU vector of ", B);
+  const int rc = launch_sac_actor_rows(
+      q_new.data_ptr<float>(), logp_new.data_ptr<float>(),
+      (long)logp_new.stride(0), check_sac_log_alpha(log_alpha),
+      (float)target_entropy, actor_rows.data_ptr<float>(),
+      alpha_rows.data_ptr<float>(), argmin.data_ptr<int>(),
+      entropy_rows.data_ptr<float>(), (int)Q, (int)B, cur_stream());
+  TORCH_CHECK(rc == 0, "sac_actor_rows: sizes outside the kernel's range");
+}
+
+// Critic half: g_rows, dq -> dq_pred. The actor half's tensors are unused.
+void sac_critic_rows_bwd(torch::Tensor g_rows, torch::Tensor dq,
+                         torch::Tensor dq_pred) {
+  TORCH_CHECK(dq.dim() == 2, "dq must be [Q, B]");
+  const int64_t Q = dq.size(0), B = dq.size(1);
+  check_sac_q(dq, "dq", Q, B);
+  check_sac_q(dq_pred, "dq_pred", Q, B);
+  check_c51_vector(g_rows, "g_rows", torch::kFloat32, B);
+  const int rc = launch_sac_rows_bwd(
+      g_rows.data_ptr<float>(), (long)g_rows.stride(0), dq.data_ptr<float>(),
+      dq_pred.data_ptr<float>(), nullptr, 0, nullptr, 0, nullptr, nullptr, 0,
+      nullptr, 0.f, nullptr, nullptr, nullptr, (int)Q, (int)B, cur_stream());
+  TORCH_CHECK(rc == 0, "sac_critic_rows_bwd: sizes outside the kernel's range");
+}
+
+// Actor half: g_actor, g_alpha -> dq_new, dlogp_new, dla_rows.
+void sac_actor_rows_bwd(torch::Tensor g_actor, torch::Tensor g_alpha,
+                        torch::Tensor argmin, torch::Tensor logp_new,
+                        torch::Tensor log_alpha, double target_entropy,
+                        torch::Tensor dq_new, torch::Tensor dlogp_new,
+                        torch::Tensor dla_rows) {
+  TORCH_CHECK(dq_new.dim() == 2, "dq_new must be [Q, B]");
+  const int64_t Q = dq_new.size(0), B = dq_new.size(1);
+  check_sac_q(dq_new, "dq_new", Q, B);
+  check_c51_vector(g_actor, "g_actor", torch::kFloat32, B);
+  check_c51_vector(g_alpha, "g_alpha", torch::kFloat32, B);
+  check_c51_vector(logp_new, "logp_new", torch::kFloat32, B);
+  check_c51_rows(dlogp_new, "dlogp_new", B, 1);
+  check_c51_rows(dla_rows, "dla_rows", B, 1);
+  TORCH_CHECK(argmin.is_cuda() && argmin.is_contiguous() &&
+                  argmin.scalar_type() == torch::kInt32 && argmin.numel() == B,
+              "argmin must be a contiguous int32 GPU vector of ", B);
+  const int rc = launch_sac_rows_bwd(
+      nullptr, 0, nullptr, nullptr, g_actor.data_ptr<float>(),
+      (long)g_actor.stride(0), g_alpha.data_ptr<float>(),
+      (long)g_alpha.stride(0), argmin.data_ptr<int>(),
+      logp_new.data_ptr<float>(), (long)logp_new.stride(0),
+      check_sac_log_alpha(log_alpha), (float)target_entropy,
+      dq_new.data_ptr<float>(), dlogp_new.data_ptr<float>(),
+      dla_rows.data_ptr<float>(), (int)Q, (int)B, cur_stream());
+  TORCH_CHECK(rc == 0, "sac_actor_rows_bwd: sizes outside the kernel's range");
+}
+
 // Argument checks shared by the NoisyLinear launchers (noisy.hip): the fp32
 // parameters mu_w / sigma_w [N, K] contiguous and 16-byte aligned, the noise
 // vectors fp32 views of the NoiseBank buffer (any offset, unit stride), and
@@ -1490,6 +1657,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "pass giving the per-row loss and d loss / d source quantile");
   m.def("qr_loss_bwd", &qr_loss_bwd,
         "QR-DQN quantile loss: scatter of the saved gradient to [B, N, A]");
+  m.def("tanh_normal_rsample_fwd", &tanh_normal_rsample_fwd,
+        "tanh-squashed affine Gaussian: sample a, logp and the saved tanh(u)");
+  m.def("tanh_normal_rsample_bwd", &tanh_normal_rsample_bwd,
+        "tanh-squashed affine Gaussian: closed-form dloc and dscale");
+  m.def("sac_critic_rows", &sac_critic_rows,
+        "SAC: soft TD target, per-row twin-Q squared error and q_pred - target");
+  m.def("sac_actor_rows", &sac_actor_rows,
+        "SAC: per-row actor term, temperature dual term, argmin and entropy");
+  m.def("sac_critic_rows_bwd", &sac_critic_rows_bwd,
+        "SAC: dq_pred from the per-row gradient (sac_rows_bwd_kernel)");
+  m.def("sac_actor_rows_bwd", &sac_actor_rows_bwd,
+        "SAC: dq_new, dlogp_new and the rows of dlog_alpha (sac_rows_bwd_kernel)");
   m.def("noisy_linear_fwd", &noisy_linear_fwd,
         "NoisyLinear forward, the noisy weight formed while staging");
   m.def("noisy_linear_dgrad", &noisy_linear_dgrad,

@@ -286,6 +286,40 @@ int launch_qr_loss_bwd(const float* grad, long grad_stride, const float* gth,
                        const long* a_tm1, long a_stride, void* dsrc, int B,
                        int N, int A, int is_bf16, void* stream);
 
+// ---- tanh_normal.hip. loc / scale / a / da / dloc / dscale are fp32 or bf16
+// [B, A] with contiguous rows (a, da, dloc in loc's dtype, dscale in
+// scale's); t may be null in the forward (not saved). The SAC row kernels
+// take fp32 [Q, B] critic values, 1 <= Q <= 4; per-row vectors come with an
+// element stride; log_alpha is one fp32 value in device memory. All return 0
+// after the launch, 1 for sizes the kernels do not take (1 <= A <= 64),
+// launching nothing. launch_sac_rows_bwd runs the critic half (g_rows set,
+// g_actor null) or the actor half (the reverse).
+int launch_tanh_normal_rsample_fwd(
+    const void* loc, const void* scale, const float* eps, void* a, float* logp,
+    float* t, int B, int A, int loc_bf16, int scale_bf16, float scale_affine,
+    float shift_affine, void* stream);
+int launch_tanh_normal_rsample_bwd(
+    const void* da, const float* dlogp, long dlogp_stride, const float* t,
+    const float* eps, const void* scale, void* dloc, void* dscale, int B,
+    int A, int loc_bf16, int scale_bf16, float scale_affine, void* stream);
+int launch_sac_critic_rows(
+    const float* q_pred, const float* q_next, const float* logp_next,
+    long lp_stride, const float* r_t, long r_stride, const float* d_t,
+    long d_stride, const float* log_alpha, float gamma, float* target,
+    float* rows, float* dq, int Q, int B, void* stream);
+int launch_sac_actor_rows(
+    const float* q_new, const float* logp_new, long lp_stride,
+    const float* log_alpha, float target_entropy, float* actor_rows,
+    float* alpha_rows, int* argmin, float* entropy_rows, int Q, int B,
+    void* stream);
+int launch_sac_rows_bwd(
+    const float* g_rows, long g_rows_stride, const float* dq, float* dq_pred,
+    const float* g_actor, long g_actor_stride, const float* g_alpha,
+    long g_alpha_stride, const int* argmin, const float* logp_new,
+    long lp_stride, const float* log_alpha, float target_entropy,
+    float* dq_new, float* dlogp_new, float* dla_rows, int Q, int B,
+    void* stream);
+
 // ---- mcts.hip
 void launch_mcts_select(
     const float* visit, const float* value_sum, const float* reward,

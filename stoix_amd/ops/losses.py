@@ -714,3 +714,174 @@ def quantile_q_learning(
     ).squeeze(-1)
     target = (r_t.unsqueeze(-1) + d_t.unsqueeze(-1) * target_dist).detach()
     return quantile_regression_loss(q_a, tau_q_tm1, target, huber_param)
+
+
+# ----------------------------- fused SAC loss rows (tanh_normal.hip)
+
+_SAC_MAX_CRITICS = 4
+
+
+def sac_fused_enabled() -> bool:
+    """STOIX_FUSED_SAC=0 forces the torch chain on the GPU for the
+    tanh-Normal sample and for the two SAC loss functions below (A/B timing)."""
+    return os.environ.get("STOIX_FUSED_SAC", "1") != "0"
+
+
+def _sac_route_to_kernel(q: Tensor, log_alpha: Tensor, rows=(), twin=None) -> bool:
+    """Whether a SAC loss below hands its inputs to the HIP kernels: knob on,
+    fp32 GPU critic values [Q, B] with 1 <= Q <= 4 (``twin`` of the same
+    shape), a one-element fp32 GPU log_alpha and fp32 GPU per-row vectors [B]."""
+    if not sac_fused_enabled() or not isinstance(q, Tensor) or q.dim() != 2:
+        return False
+    Q, B = q.shape
+    if not 1 <= Q <= _SAC_MAX_CRITICS or B < 1:
+        return False
+    for t in (q,) if twin is None else (q, twin):
+        if not t.is_cuda or t.dtype != torch.float32 or t.shape != (Q, B):
+            return False
+    if not (
+        isinstance(log_alpha, Tensor)
+        and log_alpha.is_cuda
+        and log_alpha.dtype == torch.float32
+        and log_alpha.numel() == 1
+    ):
+        return False
+    return all(
+        isinstance(v, Tensor) and v.is_cuda and v.dtype == torch.float32 and v.shape == (B,)
+        for v in rows
+    )
+
+
+class _SACCriticRows(torch.autograd.Function):
+    """Soft TD target and per-row twin-Q squared error, GPU only
+    (sac_critic_rows_kernel); the gradient goes to q_pred alone, through the
+    saved ``q_pred - target`` (sac_rows_bwd_kernel)."""
+
+    @staticmethod
+    def forward(ctx, q_pred, q_next, logp_next, r_t, d_t, log_alpha, gamma):
+        from stoix_amd.ops import ext
+
+        Q, B = q_pred.shape
+        dev = q_pred.device
+        target = torch.empty(B, dtype=torch.float32, device=dev)
+        rows = torch.empty(B, dtype=torch.float32, device=dev)
+        dq = torch.empty(Q, B, dtype=torch.float32, device=dev)
+        ext(required=True).sac_critic_rows(
+            q_pred.contiguous(), q_next.contiguous(), logp_next, r_t, d_t,  # rows may be strided
+            log_alpha.detach(), float(gamma), target, rows, dq,
+        )
+        ctx.save_for_backward(dq)
+        ctx.mark_non_differentiable(target)
+        return rows, target
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rows, _g_target):
+        from stoix_amd.ops import ext
+
+        (dq,) = ctx.saved_tensors
+        dq_pred = torch.empty_like(dq)
+        ext(required=True).sac_critic_rows_bwd(g_rows, dq, dq_pred)
+        return dq_pred, None, None, None, None, None, None
+
+
+class _SACActorRows(torch.autograd.Function):
+    """Per-row actor term, temperature dual term and entropy, GPU only
+    (sac_actor_rows_kernel). Gradients: the arg-min critic of q_new and
+    logp_new from the actor term (alpha a constant), log_alpha from the dual
+    (logp_new a constant), all from sac_rows_bwd_kernel."""
+
+    @staticmethod
+    def forward(ctx, q_new, logp_new, log_alpha, target_entropy):
+        from stoix_amd.ops import ext
+
+        Q, B = q_new.shape
+        dev = q_new.device
+        actor_rows, alpha_rows, entropy_rows = (
+            torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3)
+        )
+        argmin = torch.empty(B, dtype=torch.int32, device=dev)
+        ext(required=True).sac_actor_rows(
+            q_new.contiguous(), logp_new, log_alpha, float(target_entropy),
+            actor_rows, alpha_rows, argmin, entropy_rows,
+        )
+        ctx.save_for_backward(argmin, logp_new, log_alpha)
+        ctx.target_entropy = float(target_entropy)
+        ctx.Q = Q
+        ctx.mark_non_differentiable(entropy_rows)
+        return actor_rows, alpha_rows, entropy_rows
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_actor, g_alpha, _g_entropy):
+        from stoix_amd.ops import ext
+
+        argmin, logp_new, log_alpha = ctx.saved_tensors
+        B = logp_new.shape[0]
+        dev = logp_new.device
+        dq_new = torch.empty(ctx.Q, B, dtype=torch.float32, device=dev)
+        dlogp_new = torch.empty(B, dtype=torch.float32, device=dev)
+        dla_rows = torch.empty(B, dtype=torch.float32, device=dev)
+        ext(required=True).sac_actor_rows_bwd(
+            g_actor, g_alpha, argmin, logp_new, log_alpha, ctx.target_entropy,
+            dq_new, dlogp_new, dla_rows,
+        )
+        dla = dla_rows.sum().reshape(log_alpha.shape) if ctx.needs_input_grad[2] else None
+        return dq_new, dlogp_new, dla, None
+
+
+def sac_critic_loss(
+    q_pred: Tensor,
+    q_next: Tensor,
+    logp_next: Tensor,
+    r_t: Tensor,
+    d_t: Tensor,
+    log_alpha: Tensor,
+    gamma: float,
+) -> Tuple[Tensor, Tensor]:
+    """SAC critic loss and its soft TD target (Haarnoja et al. 2018).
+
+    ``q_pred`` / ``q_next`` [Q, B] (online critics at the stored action,
+    target critics at a fresh next action), ``logp_next`` / ``r_t`` / ``d_t``
+    [B]: ``target = r + gamma * d * (min_q q_next - alpha * logp_next)``, a
+    constant; ``loss = 0.5 * mean((q_pred - target)^2)`` over all Q * B.
+    Returns ``(loss, target)``.
+
+    On the GPU, fp32 inputs with at most 4 critics run in tanh_normal.hip
+    (one kernel forward, one backward, log_alpha read on the device); the CPU,
+    anything else, or STOIX_FUSED_SAC=0 runs the torch expressions.
+    """
+    if _sac_route_to_kernel(q_pred, log_alpha, (logp_next, r_t, d_t), twin=q_next):
+        rows, target = _SACCriticRows.apply(
+            q_pred, q_next.detach(), logp_next.detach(), r_t, d_t, log_alpha, gamma
+        )
+        return rows.mean() / q_pred.shape[0], target
+    alpha = log_alpha.exp().detach()
+    with torch.no_grad():
+        target = r_t + gamma * d_t * (q_next.min(dim=0).values - alpha * logp_next)
+    return 0.5 * ((q_pred - target.unsqueeze(0)) ** 2).mean(), target
+
+
+def sac_actor_alpha_losses(
+    q_new: Tensor,
+    logp_new: Tensor,
+    log_alpha: Tensor,
+    target_entropy: float,
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """SAC actor loss ``mean(alpha * logp_new - min_q q_new)`` (alpha a
+    constant), temperature dual ``-mean(log_alpha * sg(logp_new + H*))`` and
+    the entropy estimate ``-mean(logp_new)`` (detached).
+
+    ``q_new`` [Q, B] are the online critics at the reparameterised action,
+    ``logp_new`` [B] its log-probability. Returns
+    ``(actor_loss, alpha_loss, entropy)``. Routed as sac_critic_loss.
+    """
+    if _sac_route_to_kernel(q_new, log_alpha, (logp_new,)):
+        actor_rows, alpha_rows, entropy_rows = _SACActorRows.apply(
+            q_new, logp_new, log_alpha, target_entropy
+        )
+        return actor_rows.mean(), alpha_rows.mean(), entropy_rows.mean()
+    alpha = log_alpha.exp().detach()
+    actor_loss = (alpha * logp_new - q_new.min(dim=0).values).mean()
+    alpha_loss = -(log_alpha * (logp_new + target_entropy).detach()).mean()
+    return actor_loss, alpha_loss, -logp_new.mean().detach()

@@ -5,6 +5,14 @@ soft target ``r + gamma*d*(min Q' - alpha*logpi(a'))`` with a fresh sample
 (:173-199), actor loss ``alpha*logpi - min Q`` via rsample (:201-221),
 autotuned temperature with ``target_entropy = -scale*action_dim`` and dual
 loss ``-log_alpha * sg(logpi + H*)`` (:151-171, 406-411).
+
+On the GPU the three ``sample_and_log_prob`` calls of an epoch run in the
+tanh-Normal kernels of ``ops/csrc/tanh_normal.hip`` (one launch forward, one
+backward for the call that needs gradients), and the soft TD target, twin-Q
+error, twin-min actor term and temperature dual in its SAC row kernels
+(``ops.losses.sac_critic_loss`` / ``sac_actor_alpha_losses``; ``log_alpha`` is
+read on the device, so the update stays capturable). ``STOIX_FUSED_SAC=0``
+restores the torch chain for all of it.
 """
 from __future__ import annotations
 
@@ -20,6 +28,7 @@ from stoix_amd.config import compose
 from stoix_amd.envs.env import StatefulVecEnv, get_final_step_metrics
 from stoix_amd.networks.base import MultiNetwork
 from stoix_amd.networks.factory import build_actor, build_critic
+from stoix_amd.ops.losses import sac_actor_alpha_losses, sac_critic_loss
 from stoix_amd.parallel.dist import FlatGradReducer, broadcast_module
 from stoix_amd.systems.anakin import run_anakin_experiment
 
@@ -125,29 +134,28 @@ class SACLearner:
         tau = float(self.sys.tau)
         for _ in range(int(self.sys.epochs)):
             batch = self.buffer.sample(self.batch_size)
-            alpha = self.log_alpha.exp().detach()
 
             # ---- critic update
             with torch.no_grad():
                 next_dist = self.actor(batch["next_obs"])
                 a_next, logp_next = next_dist.sample_and_log_prob(self.gen)
-                q_next = self.q_target(batch["next_obs"], a_next).min(dim=0).values
-                target = batch["reward"] + self.gamma * batch["discount"] * (
-                    q_next - alpha * logp_next
-                )
+                q_next = self.q_target(batch["next_obs"], a_next)  # [2, B]
             q_pred = self.q_online(batch["obs"], batch["action"])  # [2, B]
-            q_loss = 0.5 * ((q_pred - target.unsqueeze(0)) ** 2).mean()
+            q_loss, _ = sac_critic_loss(
+                q_pred, q_next, logp_next, batch["reward"], batch["discount"],
+                self.log_alpha, self.gamma,
+            )
 
-            # ---- actor update (pathwise, twin-min)
+            # ---- actor update (pathwise, twin-min) and temperature dual
             dist = self.actor(batch["obs"])
             a_new, logp_new = dist.sample_and_log_prob(self.gen)
-            q_new = self.q_online(batch["obs"], a_new).min(dim=0).values
-            actor_loss = (alpha * logp_new - q_new).mean()
-
-            # ---- temperature dual
-            if self.autotune:
-                alpha_loss = -(self.log_alpha * (logp_new + self.target_entropy).detach()).mean()
-            else:
+            q_new = self.q_online(batch["obs"], a_new)  # [2, B]
+            # a fixed temperature takes no gradient: log_alpha.grad stays None
+            log_alpha = self.log_alpha if self.autotune else self.log_alpha.detach()
+            actor_loss, alpha_loss, entropy = sac_actor_alpha_losses(
+                q_new, logp_new, log_alpha, self.target_entropy
+            )
+            if not self.autotune:
                 alpha_loss = torch.zeros((), device=self.device)
 
             self.actor_opt.zero_grad(set_to_none=True)
@@ -172,7 +180,7 @@ class SACLearner:
                 "q_loss": q_loss.detach(),
                 "actor_loss": actor_loss.detach(),
                 "alpha": self.log_alpha.exp().detach(),
-                "entropy": -logp_new.mean().detach(),
+                "entropy": entropy,
             }
         return metrics
 
