@@ -62,13 +62,21 @@ class CompositeNetwork(nn.Module):
 
 class MultiNetwork(nn.Module):
     """N copies of a network evaluated on the same input, outputs stacked on
-    a leading 'ensemble' dim (twin critics; reference base.py:88-121)."""
+    a leading 'ensemble' dim (twin critics; reference base.py:88-121).
+
+    An ensemble of fp32 obs-action MLP critics on the GPU runs every layer of
+    all members in one launch (ops/qens.py, ``STOIX_FUSED_QENS``); anything
+    else evaluates the members one after the other."""
 
     def __init__(self, networks: Sequence[nn.Module]):
         super().__init__()
         self.networks = nn.ModuleList(networks)
 
     def forward(self, *inputs: Any) -> Tensor:
+        from stoix_amd.ops.qens import qens_forward, qens_route_to_kernel
+
+        if qens_route_to_kernel(self, inputs):
+            return qens_forward(self, inputs)
         outs = [net(*inputs) for net in self.networks]
         return torch.stack(outs, dim=0)
 

@@ -1365,6 +1365,167 @@ void noise_transform(torch::Tensor x) {
   launch_noise_transform(x.data_ptr<float>(), (long)x.numel(), cur_stream());
 }
 
+// Argument checks shared by the Q-ensemble launchers (qens.hip). A dtype or a
+// member count the kernels do not take makes the call ineligible (false,
+// nothing launched); tensors on the wrong device, of the wrong shape or not
+// contiguous are errors.
+bool qens_f32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name,
+              " must be a contiguous GPU tensor");
+  return t.scalar_type() == torch::kFloat32;
+}
+
+// E same-shaped fp32 tensors -> one pointer per member. False: ineligible.
+template <typename Members>
+bool qens_members(const std::vector<torch::Tensor>& ts, const char* name,
+                  c10::IntArrayRef shape, Members* out) {
+  const size_t E = ts.size();
+  if (E < 1 || E > QENS_MAX_E) return false;
+  for (size_t e = 0; e < QENS_MAX_E; ++e) out->p[e] = nullptr;
+  for (size_t e = 0; e < E; ++e) {
+    if (!qens_f32(ts[e], name)) return false;
+    TORCH_CHECK(ts[e].sizes() == shape, name, ": member ", e, " has shape ",
+                ts[e].sizes(), ", expected ", shape);
+    out->p[e] = ts[e].data_ptr<float>();
+  }
+  return true;
+}
+
+// The two input pieces: X0 [S, K0] (shared) or [E, S, K0], X1 [S, K1] or empty.
+struct QensInput {
+  const float *x0, *x1;
+  int64_t x0_es, S, K0, K1;
+};
+
+bool qens_input(const torch::Tensor& X0, const torch::Tensor& X1, int64_t E,
+                QensInput* in) {
+  if (!qens_f32(X0, "X0")) return false;
+  TORCH_CHECK(X0.dim() == 2 || (X0.dim() == 3 && X0.size(0) == E),
+              "X0 must be [S, K0] or [E, S, K0]");
+  in->S = X0.size(-2);
+  in->K0 = X0.size(-1);
+  in->x0_es = X0.dim() == 3 ? in->S * in->K0 : 0;
+  in->x0 = X0.data_ptr<float>();
+  in->x1 = nullptr;
+  in->K1 = 0;
+  if (X1.numel() > 0) {
+    if (!qens_f32(X1, "X1")) return false;
+    TORCH_CHECK(X1.dim() == 2 && X1.size(0) == in->S, "X1 must be [S, K1]");
+    in->K1 = X1.size(1);
+    in->x1 = X1.data_ptr<float>();
+  }
+  return in->S >= 1 && in->K0 >= 1 && in->S < (1LL << 31) - 64;
+}
+
+// dH and the saved H / Z: contiguous fp32 [E, S, N]; aux empty for act 0.
+bool qens_dh(const torch::Tensor& dH, const torch::Tensor& aux, int64_t act,
+             const float** ax) {
+  TORCH_CHECK(dH.dim() == 3, "dH must be [E, S, N]");
+  if (!qens_f32(dH, "dH")) return false;
+  *ax = nullptr;
+  if (act != 0) {
+    if (!qens_f32(aux, "aux")) return false;
+    TORCH_CHECK(aux.sizes() == dH.sizes(), "aux must have dH's shape");
+    *ax = aux.data_ptr<float>();
+  }
+  return dH.numel() > 0;
+}
+
+// An output of rows [.., S, cols] that may be a view with margins: unit
+// element stride, any row and member stride.
+void check_qens_out(const torch::Tensor& t, const char* name, int64_t E,
+                    int64_t S, int64_t cols) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32, name,
+              " must be an fp32 GPU tensor");
+  const bool ok3 = t.dim() == 3 && t.size(0) == E;
+  TORCH_CHECK((ok3 || (E == 1 && t.dim() == 2)) && t.size(-2) == S &&
+                  t.size(-1) == cols && (t.stride(-1) == 1 || cols == 1),
+              name, " must be [", E, ", ", S, ", ", cols,
+              "] with unit element stride");
+}
+
+// H [E, S, N] = act([X0 | X1] W_e^T + b_e) for every member in one launch; Z
+// (empty: not written) takes the pre-activation. False: ineligible.
+bool qens_linear_fwd(torch::Tensor X0, torch::Tensor X1,
+                     std::vector<torch::Tensor> W, std::vector<torch::Tensor> b,
+                     torch::Tensor Z, torch::Tensor H, int64_t act) {
+  const int64_t E = (int64_t)W.size();
+  QensInput in;
+  if (E < 1 || E > QENS_MAX_E || b.size() != W.size() ||
+      !qens_input(X0, X1, E, &in))
+    return false;
+  TORCH_CHECK(W[0].dim() == 2 && W[0].size(1) == in.K0 + in.K1,
+              "W must be [N, K0 + K1]");
+  const int64_t N = W[0].size(0);
+  QensIn Wp, Bp;
+  if (!qens_members(W, "W", {N, in.K0 + in.K1}, &Wp) ||
+      !qens_members(b, "b", {N}, &Bp))
+    return false;
+  check_qens_out(H, "H", E, in.S, N);
+  float* zp = nullptr;
+  if (Z.numel() > 0) {
+    check_qens_out(Z, "Z", E, in.S, N);
+    TORCH_CHECK(Z.strides() == H.strides(), "Z must have H's strides");
+    zp = Z.data_ptr<float>();
+  }
+  return launch_qens_linear_fwd(
+             in.x0, (long)in.x0_es, in.x1, Wp, Bp, zp, H.data_ptr<float>(),
+             (long)H.stride(-2), H.dim() == 3 ? (long)H.stride(0) : 0L,
+             (int)in.S, (int)in.K0, (int)in.K1, (int)N, (int)E, (int)act,
+             cur_stream()) == 0;
+}
+
+// dX = (dH * act'(aux)) @ W_e[:, c0 : c0 + dX.size(-1)]: per member into dX
+// [E, S, .], or with summed over the members into dX [S, .].
+bool qens_linear_dgrad(torch::Tensor dH, torch::Tensor aux,
+                       std::vector<torch::Tensor> W, torch::Tensor dX,
+                       int64_t c0, int64_t act, bool summed) {
+  const float* ax;
+  if (!qens_dh(dH, aux, act, &ax)) return false;
+  const int64_t E = dH.size(0), S = dH.size(1), N = dH.size(2);
+  if (W.empty() || (int64_t)W.size() != E) return false;
+  TORCH_CHECK(W[0].dim() == 2 && W[0].size(0) == N, "W must be [N, K]");
+  const int64_t K = W[0].size(1), KW = dX.size(-1);
+  QensIn Wp;
+  if (!qens_members(W, "W", {N, K}, &Wp)) return false;
+  check_qens_out(dX, "dX", summed ? 1 : E, S, KW);
+  TORCH_CHECK(c0 >= 0 && KW >= 1 && c0 + KW <= K, "column range outside W");
+  return launch_qens_linear_dgrad(
+             dH.data_ptr<float>(), ax, Wp, dX.data_ptr<float>(),
+             (long)dX.stride(-2), dX.dim() == 3 ? (long)dX.stride(0) : 0L,
+             (int)S, (int)K, (int)N, (int)c0, (int)(c0 + KW), (int)E,
+             summed ? 1 : 0, (int)act, cur_stream()) == 0;
+}
+
+// dW_e = (dH_e * act'(aux_e))^T [X0 | X1] and db_e = its column sums, written
+// into the members' gradient tensors.
+bool qens_linear_wgrad(torch::Tensor dH, torch::Tensor aux, torch::Tensor X0,
+                       torch::Tensor X1, std::vector<torch::Tensor> dW,
+                       std::vector<torch::Tensor> db, int64_t act) {
+  const float* ax;
+  if (!qens_dh(dH, aux, act, &ax)) return false;
+  const int64_t E = dH.size(0), S = dH.size(1), N = dH.size(2);
+  QensInput in;
+  if ((int64_t)dW.size() != E || db.size() != dW.size() ||
+      !qens_input(X0, X1, E, &in))
+    return false;
+  TORCH_CHECK(in.S == S, "X0 and dH disagree on S");
+  const int64_t K = in.K0 + in.K1;
+  QensOut Wg, Bg;
+  if (!qens_members(dW, "dW", {N, K}, &Wg) ||
+      !qens_members(db, "db", {N}, &Bg))
+    return false;
+  int slices, s_per;
+  long slab_stride;
+  qens_wgrad_geometry((int)S, (int)K, (int)N, &slices, &s_per, &slab_stride);
+  torch::Tensor slab =
+      torch::empty({E * (int64_t)slices * slab_stride}, dH.options());
+  return launch_qens_linear_wgrad(
+             dH.data_ptr<float>(), ax, in.x0, (long)in.x0_es, in.x1,
+             slab.data_ptr<float>(), Wg, Bg, (int)S, (int)in.K0, (int)in.K1,
+             (int)N, (int)E, (int)act, cur_stream()) == 0;
+}
+
 // Argument checks shared by the two MCTS launchers (mcts.hip): the arena of
 // search/mcts.py, contiguous on one GPU, B trees x N node slots x A actions.
 struct MctsShape {
@@ -1677,6 +1838,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NoisyLinear mu/sigma weight and bias gradients (split-S + reduce)");
   m.def("noise_transform", &noise_transform,
         "in-place f(x) = sign(x) sqrt(|x|) over the NoiseBank buffer");
+  m.def("qens_linear_fwd", &qens_linear_fwd,
+        "Q-ensemble dense layer forward, all members in one launch (fp32)");
+  m.def("qens_linear_dgrad", &qens_linear_dgrad,
+        "Q-ensemble input gradient, per member or summed over members");
+  m.def("qens_linear_wgrad", &qens_linear_wgrad,
+        "Q-ensemble weight and bias gradients (split-S + reduce)");
   m.def("snake_step", &snake_step,
         "fused Snake env step (dynamics + metrics + autoreset + render)");
   m.def("rnn_scan", &rnn_scan,

@@ -55,6 +55,17 @@ struct LinSiluNet {
   void* H;            // bf16 [S, N]
 };
 
+// The members of a Q-ensemble layer (qens.hip): one pointer per member for an
+// operand that stays in the members' own tensors (weights, biases, their
+// gradients). Entries past the member count are not read.
+#define QENS_MAX_E 4
+struct QensIn {
+  const float* p[QENS_MAX_E];
+};
+struct QensOut {
+  float* p[QENS_MAX_E];
+};
+
 extern "C" {
 
 // ---- envs.hip. The three step launchers take one parameter list, written
@@ -355,5 +366,33 @@ int launch_noisy_linear_wgrad(
     float* dsigma_b, int S, int K, int N, int dz_bf16, int x_bf16,
     void* stream);
 void launch_noise_transform(float* x, long n, void* stream);
+
+// ---- qens.hip. fp32 throughout, E members (1..QENS_MAX_E). act: 0 none, 1
+// SiLU, 2 ReLU. The layer input is [X0 | X1]: X0 [S, K0] with member stride
+// x0_es in floats (0: one X0 for all members), X1 [S, K1] shared or null with
+// K1 == 0. Outputs are rows with unit element stride, a row stride and a
+// member stride in floats. All return 0 after the launch, 1 for sizes the
+// kernels do not take (an empty dimension, E outside 1..4), launching nothing.
+// Z: null, or written next to H (SiLU only).
+int launch_qens_linear_fwd(const float* X0, long x0_es, const float* X1,
+                           const QensIn& W, const QensIn& B, float* Z,
+                           float* H, long out_ld, long out_es, int S, int K0,
+                           int K1, int N, int E, int act, void* stream);
+// dX = (dH * act'(AUX)) @ W[:, c0:c1): per member into [E, S, c1-c0], or with
+// summed != 0 added over the members in ascending order into [S, c1-c0].
+// AUX is the layer's H (ReLU) or Z (SiLU), [E, S, N] as dH; null for act 0.
+int launch_qens_linear_dgrad(const float* dH, const float* AUX,
+                             const QensIn& W, float* dX, long dx_ld,
+                             long dx_es, int S, int K, int N, int c0, int c1,
+                             int E, int summed, int act, void* stream);
+// Slices of S the wgrad runs with and the fp32 elements of one slab image.
+void qens_wgrad_geometry(int S, int K, int N, int* slices, int* s_per,
+                         long* slab_stride);
+// slab holds E * slices * slab_stride floats, 16-byte aligned.
+int launch_qens_linear_wgrad(const float* dH, const float* AUX,
+                             const float* X0, long x0_es, const float* X1,
+                             float* slab, const QensOut& dW, const QensOut& dB,
+                             int S, int K0, int K1, int N, int E, int act,
+                             void* stream);
 
 }  // extern "C"
