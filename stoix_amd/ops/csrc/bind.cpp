@@ -1526,6 +1526,153 @@ bool qens_linear_wgrad(torch::Tensor dH, torch::Tensor aux, torch::Tensor X0,
              (int)N, (int)E, (int)act, cur_stream()) == 0;
 }
 
+// The by-value table of the multi-tensor optimiser tail (multi_adam.hip),
+// built from the tensors torch's Adam owns: pointer reads only, no device
+// sync and nothing copied to the device. Tensor i belongs to chain
+// chain_of[i] (non-decreasing); hyper[c] = {beta1, beta2, eps, lr, max_norm,
+// clip, tau}; lr_tensors[c] replaces hyper[c][3] when the param group holds a
+// tensor. False: the call is ineligible (more tensors, chains or chunks than
+// the table takes, a tensor that is not contiguous fp32 on partials' device)
+// and nothing may be launched. Mismatched list lengths are errors.
+using OptTensors = std::vector<c10::optional<torch::Tensor>>;
+
+bool madam_f32(const torch::Tensor& t, const torch::Device& dev) {
+  return t.is_cuda() && t.device() == dev &&
+         t.scalar_type() == torch::kFloat32 && t.is_contiguous();
+}
+
+bool madam_table(const std::vector<torch::Tensor>& params,
+                 const OptTensors& grads,
+                 const OptTensors& exp_avgs,
+                 const OptTensors& exp_avg_sqs,
+                 const OptTensors& steps,
+                 const OptTensors& targets,
+                 const std::vector<int64_t>& chain_of,
+                 const std::vector<std::vector<double>>& hyper,
+                 const OptTensors& lr_tensors, const torch::Tensor& partials,
+                 MultiAdamTable* T) {
+  const size_t n = params.size(), nc = hyper.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_sqs.size() == n && steps.size() == n &&
+                  targets.size() == n && chain_of.size() == n,
+              "multi_adam: one entry per tensor in every list");
+  TORCH_CHECK(lr_tensors.size() == nc, "multi_adam: one lr entry per chain");
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+                  partials.scalar_type() == torch::kFloat32,
+              "multi_adam: partials must be a contiguous fp32 GPU tensor");
+  if (n > MADAM_MAX_TENSORS || nc > MADAM_MAX_CHAINS) return false;
+  const torch::Device dev = partials.device();
+  std::memset(T, 0, sizeof(*T));
+
+  for (size_t c = 0; c < nc; ++c) {
+    TORCH_CHECK(hyper[c].size() == 7, "multi_adam: 7 values per chain");
+    MultiAdamChain& ch = T->c[c];
+    const double b1 = hyper[c][0], b2 = hyper[c][1], tau = hyper[c][6];
+    ch.b1 = (float)b1;
+    ch.b2 = (float)b2;
+    ch.omb1 = (float)(1.0 - b1);
+    ch.omb2 = (float)(1.0 - b2);
+    ch.eps = (float)hyper[c][2];
+    ch.lr = (float)hyper[c][3];
+    ch.max_norm = (float)hyper[c][4];
+    ch.clip = hyper[c][5] != 0.0;
+    ch.tau = (float)tau;
+    ch.omt = (float)(1.0 - tau);
+    if (lr_tensors[c].has_value()) {
+      const torch::Tensor& lr = *lr_tensors[c];
+      if (!madam_f32(lr, dev) || lr.numel() != 1) return false;
+      ch.lr_ptr = lr.data_ptr<float>();
+    }
+  }
+
+  int64_t block = 0, prev_chain = -1;
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t c = chain_of[i];
+    TORCH_CHECK(c >= 0 && c < (int64_t)nc && c >= prev_chain,
+                "multi_adam: chain ids must ascend within [0, chains)");
+    const torch::Tensor& p = params[i];
+    const int64_t numel = p.numel();
+    if (!madam_f32(p, dev) || numel < 1) return false;
+    MultiAdamTensor& t = T->t[i];
+    t.p = p.data_ptr<float>();
+    if (grads[i].has_value()) {
+      TORCH_CHECK(exp_avgs[i].has_value() && exp_avg_sqs[i].has_value() &&
+                      steps[i].has_value(),
+                  "multi_adam: a tensor with a gradient needs its Adam state");
+      const torch::Tensor &g = *grads[i], &m = *exp_avgs[i],
+                          &v = *exp_avg_sqs[i], &st = *steps[i];
+      if (!madam_f32(g, dev) || !madam_f32(m, dev) || !madam_f32(v, dev) ||
+          !madam_f32(st, dev) || st.numel() != 1 || g.numel() != numel ||
+          m.numel() != numel || v.numel() != numel)
+        return false;
+      t.g = g.data_ptr<float>();
+      t.m = m.data_ptr<float>();
+      t.v = v.data_ptr<float>();
+      t.step = st.data_ptr<float>();
+    } else {
+      // no gradient this step: the entry is there for its polyak only
+      TORCH_CHECK(targets[i].has_value(),
+                  "multi_adam: a tensor with neither gradient nor target");
+    }
+    if (targets[i].has_value()) {
+      const torch::Tensor& tg = *targets[i];
+      if (!madam_f32(tg, dev) || tg.numel() != numel) return false;
+      t.tgt = tg.data_ptr<float>();
+    }
+    MultiAdamChain& ch = T->c[c];
+    if (c != prev_chain) ch.part_begin = (unsigned int)block;
+    const int64_t chunks = (numel + MADAM_CHUNK - 1) / MADAM_CHUNK;
+    if ((int64_t)ch.part_count + chunks > MADAM_MAX_CHUNKS) return false;
+    ch.part_count += (unsigned int)chunks;
+    t.numel = (unsigned int)numel;
+    t.first_block = (unsigned short)block;
+    t.chain = (unsigned short)c;
+    block += chunks;
+    prev_chain = c;
+  }
+  T->n_tensors = (int)n;
+  T->n_blocks = (int)block;
+  TORCH_CHECK(partials.numel() >= block, "multi_adam: partials holds ",
+              partials.numel(), " floats, the call has ", block, " blocks");
+  return true;
+}
+
+// Launch A of the tail: the per-block sums of squares of the clipped chains
+// into partials, and step + 1 into every tensor's step. False: ineligible.
+bool multi_adam_norm(std::vector<torch::Tensor> params,
+                     OptTensors grads,
+                     OptTensors exp_avgs,
+                     OptTensors exp_avg_sqs,
+                     OptTensors steps, OptTensors targets,
+                     std::vector<int64_t> chain_of,
+                     std::vector<std::vector<double>> hyper,
+                     OptTensors lr_tensors, torch::Tensor partials) {
+  MultiAdamTable T;
+  if (!madam_table(params, grads, exp_avgs, exp_avg_sqs, steps, targets,
+                   chain_of, hyper, lr_tensors, partials, &T))
+    return false;
+  launch_multi_adam_norm(T, partials.data_ptr<float>(), cur_stream());
+  return true;
+}
+
+// Launch B: clip coefficient from the partials, Adam and polyak, every tensor
+// read and written once. Takes what multi_adam_norm took.
+bool multi_adam_update(std::vector<torch::Tensor> params,
+                       OptTensors grads,
+                       OptTensors exp_avgs,
+                       OptTensors exp_avg_sqs,
+                       OptTensors steps, OptTensors targets,
+                       std::vector<int64_t> chain_of,
+                       std::vector<std::vector<double>> hyper,
+                       OptTensors lr_tensors, torch::Tensor partials) {
+  MultiAdamTable T;
+  if (!madam_table(params, grads, exp_avgs, exp_avg_sqs, steps, targets,
+                   chain_of, hyper, lr_tensors, partials, &T))
+    return false;
+  launch_multi_adam_update(T, partials.data_ptr<float>(), cur_stream());
+  return true;
+}
+
 // Argument checks shared by the two MCTS launchers (mcts.hip): the arena of
 // search/mcts.py, contiguous on one GPU, B trees x N node slots x A actions.
 struct MctsShape {
@@ -1844,6 +1991,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Q-ensemble input gradient, per member or summed over members");
   m.def("qens_linear_wgrad", &qens_linear_wgrad,
         "Q-ensemble weight and bias gradients (split-S + reduce)");
+  m.def("multi_adam_norm", &multi_adam_norm,
+        "optimiser tail, launch A: ordered grad-norm partials and step + 1 "
+        "for up to 4 chains of torch-owned tensors");
+  m.def("multi_adam_update", &multi_adam_update,
+        "optimiser tail, launch B: clip + Adam + polyak on the same table");
   m.def("snake_step", &snake_step,
         "fused Snake env step (dynamics + metrics + autoreset + render)");
   m.def("rnn_scan", &rnn_scan,

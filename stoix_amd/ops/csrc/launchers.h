@@ -66,7 +66,49 @@ struct QensOut {
   float* p[QENS_MAX_E];
 };
 
+// The multi-tensor optimiser tail (multi_adam.hip): every tensor of up to
+// MADAM_MAX_CHAINS clip + Adam (+ polyak) chains, passed to both kernels by
+// value. A chain's tensors are adjacent, in chain order; tensor i owns the
+// blocks [first_block, first_block of i + 1), one per MADAM_CHUNK elements,
+// and block b of the grid keeps its sum of squares in partials[b].
+#define MADAM_MAX_TENSORS 64
+#define MADAM_MAX_CHAINS 4
+#define MADAM_CHUNK 2048       // elements per 256-thread block
+#define MADAM_MAX_CHUNKS 4096  // blocks of one chain
+struct MultiAdamTensor {
+  float* p;
+  const float* g;  // null: no gradient this step, only tgt is updated
+  float* m;
+  float* v;
+  float* tgt;   // polyak target or null
+  float* step;  // torch's 0-dim fp32 step of this parameter
+  unsigned int numel;
+  unsigned short first_block, chain;
+};
+struct MultiAdamChain {
+  float b1, b2, omb1, omb2, eps, max_norm, tau, omt;  // omX = fl(1 - X)
+  float lr;             // used when lr_ptr is null
+  int clip;             // 0: no norm, coef = 1
+  const float* lr_ptr;  // a tensor lr, read on the device
+  unsigned int part_begin, part_count;  // the chain's blocks
+};
+struct MultiAdamTable {
+  MultiAdamTensor t[MADAM_MAX_TENSORS];
+  MultiAdamChain c[MADAM_MAX_CHAINS];
+  int n_tensors, n_blocks;
+};
+static_assert(sizeof(MultiAdamTable) <= 3968,
+              "the table is a kernel argument: 4 KB with room for the rest");
+
 extern "C" {
+
+// ---- multi_adam.hip. partials holds n_blocks floats. Launch A writes the
+// per-block sums of squares of the clipped chains and every tensor's
+// step + 1; launch B reads both.
+void launch_multi_adam_norm(const MultiAdamTable& T, float* partials,
+                            void* stream);
+void launch_multi_adam_update(const MultiAdamTable& T, const float* partials,
+                              void* stream);
 
 // ---- envs.hip. The three step launchers take one parameter list, written
 // once; only the action type differs.

@@ -14,6 +14,7 @@ from stoix_amd.buffers import ItemBuffer
 from stoix_amd.envs.env import StatefulVecEnv, get_final_step_metrics
 from stoix_amd.networks.base import MultiNetwork
 from stoix_amd.networks.factory import build_actor, build_critic
+from stoix_amd.ops.optim import OptimChain, OptimTail
 from stoix_amd.parallel.dist import FlatGradReducer, broadcast_module
 
 Tensor = torch.Tensor
@@ -53,6 +54,14 @@ class DDPGFamilyLearner:
 
         self.actor_opt = torch.optim.Adam(self.actor.parameters(), lr=float(self.sys.actor_lr), capturable=device.type == "cuda")
         self.q_opt = torch.optim.Adam(self.q_online.parameters(), lr=float(self.sys.q_lr), capturable=device.type == "cuda")
+        max_norm = getattr(self.sys, "max_grad_norm", None) or None
+        tau = float(self.sys.tau)
+        self.tail = OptimTail([
+            OptimChain(self.q_opt, self.q_online.parameters(), max_norm,
+                       self.q_target.parameters(), tau),
+            OptimChain(self.actor_opt, self.actor.parameters(), max_norm,
+                       self.actor_target.parameters(), tau),
+        ])
         self.reducer = FlatGradReducer(
             list(self.actor.parameters()) + list(self.q_online.parameters()), device
         )
@@ -144,7 +153,6 @@ class DDPGFamilyLearner:
     def update_step(self) -> Dict[str, Tensor]:
         self._rollout_into_buffer(self.T)
         metrics: Dict[str, Tensor] = {}
-        tau = float(self.sys.tau)
         freq = int(getattr(self.sys, "policy_frequency", 1))
         for _ in range(int(self.sys.epochs)):
             batch = self.buffer.sample(self.batch_size)
@@ -161,18 +169,9 @@ class DDPGFamilyLearner:
 
             self.reducer.reduce()
             self.reducer.wait()
-            if getattr(self.sys, "max_grad_norm", None):
-                nn.utils.clip_grad_norm_(self.q_online.parameters(), float(self.sys.max_grad_norm))
-                nn.utils.clip_grad_norm_(self.actor.parameters(), float(self.sys.max_grad_norm))
-            self.q_opt.step()
-            from stoix_amd.parallel.dist import polyak_update
-
-            if do_actor:
-                self.actor_opt.step()
-                with torch.no_grad():
-                    polyak_update(self.actor.parameters(), self.actor_target.parameters(), tau)
-            with torch.no_grad():
-                polyak_update(self.q_online.parameters(), self.q_target.parameters(), tau)
+            # clip + Adam + polyak of the critic chain and, on its turns, the
+            # actor chain (ops/optim.py)
+            self.tail.step(active=(True, do_actor))
             self.update_count += 1
         return metrics
 

@@ -12,7 +12,6 @@ import sys
 from typing import Dict
 
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from stoix_amd.buffers import PrioritisedBuffer
@@ -25,6 +24,7 @@ from stoix_amd.ops.losses import (
     c51_td_cross_entropy,
     categorical_l2_project,
 )
+from stoix_amd.ops.optim import OptimChain, OptimTail
 from stoix_amd.parallel.dist import FlatGradReducer, broadcast_module
 from stoix_amd.systems.anakin import run_anakin_experiment
 
@@ -66,6 +66,10 @@ class RainbowLearner:
             self.q_online.parameters(), lr=float(self.sys.q_lr), eps=1e-5,
             capturable=device.type == "cuda",
         )
+        self.tail = OptimTail([OptimChain(
+            self.opt, self.q_online.parameters(), getattr(self.sys, "max_grad_norm", None) or None,
+            self.q_target.parameters(), float(self.sys.tau),
+        )])
         self.reducer = FlatGradReducer(self.q_online.parameters(), device)
         self.gen = torch.Generator(device=device)
         self.gen.manual_seed(int(config.arch.seed) * 7919 + 503)
@@ -148,7 +152,6 @@ class RainbowLearner:
     def update_step(self) -> Dict[str, Tensor]:
         self._rollout_into_buffer(self.T)
         metrics: Dict[str, Tensor] = {}
-        tau = float(self.sys.tau)
         for _ in range(int(self.sys.epochs)):
             beta = self.beta0 + (1.0 - self.beta0) * (
                 self._update_count / self.total_updates
@@ -211,15 +214,10 @@ class RainbowLearner:
             loss.backward()
             self.reducer.reduce()
             self.reducer.wait()
-            if getattr(self.sys, "max_grad_norm", None):
-                nn.utils.clip_grad_norm_(self.q_online.parameters(), float(self.sys.max_grad_norm))
-            self.opt.step()
+            # clip + Adam + polyak (ops/optim.py)
+            self.tail.step()
             # priority writeback: per-sample TD error magnitude
             self.buffer.set_priorities(batch["_slots"], ce.detach())
-            with torch.no_grad():
-                tgt = list(self.q_target.parameters())
-                torch._foreach_mul_(tgt, 1 - tau)
-                torch._foreach_add_(tgt, list(self.q_online.parameters()), alpha=tau)
             self._update_count += 1
             metrics = {"q_loss": loss.detach(), "beta": beta.detach()}
         return metrics

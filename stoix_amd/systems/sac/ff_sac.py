@@ -21,7 +21,6 @@ import sys
 from typing import Dict
 
 import torch
-import torch.nn as nn
 
 from stoix_amd.buffers import ItemBuffer
 from stoix_amd.config import compose
@@ -29,6 +28,7 @@ from stoix_amd.envs.env import StatefulVecEnv, get_final_step_metrics
 from stoix_amd.networks.base import MultiNetwork
 from stoix_amd.networks.factory import build_actor, build_critic
 from stoix_amd.ops.losses import sac_actor_alpha_losses, sac_critic_loss
+from stoix_amd.ops.optim import OptimChain, OptimTail
 from stoix_amd.parallel.dist import FlatGradReducer, broadcast_module
 from stoix_amd.systems.anakin import run_anakin_experiment
 
@@ -70,6 +70,15 @@ class SACLearner:
         self.actor_opt = torch.optim.Adam(self.actor.parameters(), lr=float(self.sys.actor_lr), capturable=device.type == "cuda")
         self.q_opt = torch.optim.Adam(self.q_online.parameters(), lr=float(self.sys.q_lr), capturable=device.type == "cuda")
         self.alpha_opt = torch.optim.Adam([self.log_alpha], lr=float(self.sys.alpha_lr), capturable=device.type == "cuda")
+        max_norm = getattr(self.sys, "max_grad_norm", None) or None
+        chains = [
+            OptimChain(self.actor_opt, self.actor.parameters(), max_norm),
+            OptimChain(self.q_opt, self.q_online.parameters(), max_norm,
+                       self.q_target.parameters(), float(self.sys.tau)),
+        ]
+        if self.autotune:
+            chains.append(OptimChain(self.alpha_opt, [self.log_alpha]))
+        self.tail = OptimTail(chains)
         self.reducer = FlatGradReducer(
             list(self.actor.parameters()) + list(self.q_online.parameters()) + [self.log_alpha],
             device,
@@ -131,7 +140,6 @@ class SACLearner:
     def update_step(self) -> Dict[str, Tensor]:
         self._rollout_into_buffer(self.T)
         metrics: Dict[str, Tensor] = {}
-        tau = float(self.sys.tau)
         for _ in range(int(self.sys.epochs)):
             batch = self.buffer.sample(self.batch_size)
 
@@ -164,18 +172,10 @@ class SACLearner:
             (q_loss + actor_loss + alpha_loss).backward()
             self.reducer.reduce()
             self.reducer.wait()
-            if getattr(self.sys, "max_grad_norm", None):
-                nn.utils.clip_grad_norm_(self.actor.parameters(), float(self.sys.max_grad_norm))
-                nn.utils.clip_grad_norm_(self.q_online.parameters(), float(self.sys.max_grad_norm))
-            self.actor_opt.step()
-            self.q_opt.step()
-            if self.autotune:
-                self.alpha_opt.step()
-
-            with torch.no_grad():
-                from stoix_amd.parallel.dist import polyak_update
-
-                polyak_update(self.q_online.parameters(), self.q_target.parameters(), tau)
+            # clip + Adam of the three chains and the polyak of the critics:
+            # two launches of ops/csrc/multi_adam.hip with
+            # STOIX_FUSED_OPTIM=1, else the torch calls
+            self.tail.step()
             metrics = {
                 "q_loss": q_loss.detach(),
                 "actor_loss": actor_loss.detach(),
