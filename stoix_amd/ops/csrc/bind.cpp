@@ -508,6 +508,52 @@ void silu_heads_fwd(torch::Tensor Z2, torch::Tensor Wh, torch::Tensor bh,
                         HID, cur_stream());
 }
 
+// Layer-2 Linear + SiLU + heads of both nets in one launch, over the stacked
+// [2, S, HID] buffers: Z2 = H1 @ W2^T + b2 (bf16 mirror biases), H2 =
+// silu(Z2), heads and, with a non-empty vpred, the value head, as
+// silu_heads_fwd forms them. Returns false, with nothing launched, for a
+// shape the kernel does not take (S % 128 != 0, HID not 128/256): the caller
+// then runs the GEMMs and silu_heads_fwd.
+bool linear_silu_heads_pair(torch::Tensor H1, torch::Tensor W2a,
+                            torch::Tensor b2a, torch::Tensor W2c,
+                            torch::Tensor b2c, torch::Tensor Wh,
+                            torch::Tensor bh, torch::Tensor Wv,
+                            torch::Tensor bv, torch::Tensor Z2,
+                            torch::Tensor H2, torch::Tensor heads,
+                            torch::Tensor vpred) {
+  for (const torch::Tensor* t : {&H1, &b2a, &b2c, &bh, &bv, &Z2, &H2, &heads})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kBFloat16,
+                "linear_silu_heads_pair: contiguous bf16 GPU tensors expected");
+  TORCH_CHECK(H1.dim() == 3 && H1.size(0) == 2,
+              "linear_silu_heads_pair needs stacked [2, S, HID] buffers");
+  const int64_t S = H1.size(1), HID = H1.size(2);
+  TORCH_CHECK(Z2.sizes() == H1.sizes() && H2.sizes() == H1.sizes(),
+              "linear_silu_heads_pair: [2, S, HID] buffers differ in shape");
+  check_fused_weight(W2a, "W2a", HID, HID);
+  check_fused_weight(W2c, "W2c", HID, HID);
+  check_fused_weight(Wh, "Wh", 16, HID);
+  check_fused_weight(Wv.view({-1, 1}), "Wv", HID, 1);
+  TORCH_CHECK(b2a.numel() == HID && b2c.numel() == HID && bh.numel() == 16 &&
+                  bv.numel() == 1,
+              "linear_silu_heads_pair: b2 must be [HID], bh [16] and bv [1]");
+  TORCH_CHECK(heads.numel() == S * 16, "linear_silu_heads_pair: heads [S, 16]");
+  if (vpred.numel() > 0) {
+    CHK(vpred, torch::kBFloat16);
+    TORCH_CHECK(vpred.numel() == S, "linear_silu_heads_pair: vpred [S]");
+  }
+  for (const torch::Tensor* t : {&H1, &W2a, &b2a, &W2c, &b2c, &Wh, &Wv, &Z2,
+                                 &H2, &heads})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "linear_silu_heads_pair: operands must be 16-byte aligned");
+  return launch_l2_fwd_heads(H1.data_ptr(), W2a.data_ptr(), b2a.data_ptr(),
+                             W2c.data_ptr(), b2c.data_ptr(), Wh.data_ptr(),
+                             bh.data_ptr(), Wv.data_ptr(), bv.data_ptr(),
+                             Z2.data_ptr(), H2.data_ptr(), heads.data_ptr(),
+                             vptr_or_null(vpred), (int)S, (int)HID,
+                             cur_stream()) == 0;
+}
+
 void heads_bwd_silu(torch::Tensor dhead, torch::Tensor dv, torch::Tensor Wh,
                     torch::Tensor Wv, torch::Tensor Z2, torch::Tensor dZ2) {
   int HID;
@@ -2073,6 +2119,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_silu_pair", &linear_silu_pair,
         "both nets' Linear(+bias)+SiLU forward over one X, row-contiguous "
         "stores; false = shape not taken, nothing launched");
+  m.def("linear_silu_heads_pair", &linear_silu_heads_pair,
+        "both nets' layer-2 Linear(+bias)+SiLU and the heads in one launch, "
+        "W2 held in LDS; false = shape not taken, nothing launched");
   m.def("slab_reduce_norm_pair", &slab_reduce_norm_pair,
         "slab_reduce_pair + each chain's ordered squared grad norm");
   m.def("adam_pair", &adam_pair,

@@ -248,6 +248,14 @@ void launch_silu_heads_fwd(const void* Z2, const void* Wh, const void* bh,
 void launch_heads_bwd_silu(const void* dhead, const void* dv, const void* Wh,
                            const void* Wv, const void* Z2, void* dZ2, int S,
                            int HID, void* stream);
+// Layer-2 Linear + SiLU + heads over the stacked [2, S, HID] buffers, W2 held
+// in LDS. Returns 0 after the launch, 1 for a shape the kernel does not take
+// (S % 128 != 0, or a HID other than 128/256: W2 at 512 does not fit in LDS).
+int launch_l2_fwd_heads(const void* H1, const void* W2a, const void* b2a,
+                        const void* W2c, const void* b2c, const void* Wh,
+                        const void* bh, const void* Wv, const void* bv,
+                        void* Z2, void* H2, void* heads, void* vpred, int S,
+                        int HID, void* stream);
 void launch_ppo_gather(const long* idx, int mb_size, const float* obs, int OBS,
                        int OBS_PAD, const float* action, int ACT,
                        const float* logp, const float* value, const float* adv,

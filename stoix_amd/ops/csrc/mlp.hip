@@ -20,7 +20,9 @@
 //     in one launch, stored row-contiguous through LDS;
 //   * silu_heads_fwd / heads_bwd_silu: the layer-2 SiLU passes of the
 //     update with the narrow head GEMMs (N=16/1 forward, K=16/1 backward)
-//     formed from the tile the pass already holds.
+//     formed from the tile the pass already holds;
+//   * l2_fwd_heads (linear_silu_heads_pair): the layer-2 GEMM of both nets,
+//     that SiLU pass and the heads in one launch, W2 held in LDS.
 //
 // Geometry (forward kernels): one workgroup of 4 waves owns ONE 16-row
 // batch tile. Each layer's N (HID columns) is split across the waves: wave
@@ -1243,6 +1245,239 @@ extern "C" void launch_heads_bwd_silu(const void* dhead, const void* dv,
                        (const bf16_t*)dv, (const bf16_t*)Wh,
                        (const bf16_t*)Wv, (const bf16_t*)Z2, (bf16_t*)dZ2, S);
   });
+}
+
+// -------------- layer-2 Linear + SiLU + heads of both nets in one launch
+//
+// Z2 = bf16(H1 @ W2^T + b2), H2 = bf16(silu(Z2)) and the head of
+// silu_heads_fwd, for the stacked [2, S, HID] buffers (blockIdx.y = net),
+// without the Z2 round trip through memory between the GEMM and the SiLU
+// pass. Arithmetic per element: one fp32 accumulator, k-steps ascending, the
+// bf16 mirror bias added in fp32 after the chain, one rounding; SiLU on the
+// rounded Z2; the head chain is the one of silu_heads_fwd_kernel, operand for
+// operand.
+//
+// Geometry: 8 waves per workgroup, one workgroup per CU. The net's W2 stays
+// in LDS for the life of the workgroup; a wave owns L2F_MT 16-row tiles over
+// ALL HID columns and walks the row tiles with the stride of the grid, so
+// there is no barrier after the weight staging. A wave's H1 rows go from
+// memory straight into its MFMA fragments (lane l: row l & 15, 16 B at
+// k = ks*32 + (l>>4)*8) and stay in registers for the whole tile.
+//
+// W2 is the A operand, so a lane holds columns of ONE row. Which columns is
+// free: A-row m of 16-column step p (0/1) of 32-column block b is W2 row
+// b*32 + (m>>2)*8 + p*4 + (m&3) (the map of heads_bwd_silu), so after the two
+// steps of a block lane l holds columns b*32 + (l>>4)*8 + 0..7 of row l & 15.
+// That is at once a 16-byte store of Z2 and H2 and the A fragment of k-step b
+// of the head MFMA: H2 never goes through LDS. W2 is staged in that row
+// order (LDS row (2b+p)*16 + m), so a fragment read is 16 consecutive padded
+// rows, conflict-free as in the forward kernels above.
+#define L2F_WAVES 8
+#define L2F_MT 2
+
+template <int HID>
+struct L2FwdLds {
+  static constexpr int HS = HID + HPAD;
+  alignas(16) bf16_t W2[HID][HS];  // rows in fragment order (see above)
+  alignas(16) bf16_t W[16][HS];    // Wh, or Wv in row 0 and zeros below
+  alignas(16) bf16_t O[L2F_WAVES][16][16 + HPAD];  // per-wave head tile
+};
+
+template <int HID>
+__launch_bounds__(L2F_WAVES * 64) __global__ NO_PK_FP32 void l2_fwd_heads_kernel(
+    const bf16_t* __restrict__ H1,   // [2, S, HID]
+    const bf16_t* __restrict__ W2a,  // [HID, HID] row-major
+    const bf16_t* __restrict__ b2a,  // [HID] bf16 mirror
+    const bf16_t* __restrict__ W2c, const bf16_t* __restrict__ b2c,
+    const bf16_t* __restrict__ Wh,   // [16, HID]
+    const bf16_t* __restrict__ bh,   // [16] bf16 mirror
+    const bf16_t* __restrict__ Wv,   // [HID]
+    const bf16_t* __restrict__ bv,   // [1] bf16 mirror
+    bf16_t* __restrict__ Z2,         // [2, S, HID]
+    bf16_t* __restrict__ H2,         // [2, S, HID]
+    bf16_t* __restrict__ heads,      // [S, 16]
+    bf16_t* __restrict__ vpred,      // [S], or null: no value head
+    int S) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char l2f_smem[];
+  L2FwdLds<HID>& lds = *reinterpret_cast<L2FwdLds<HID>*>(l2f_smem);
+  constexpr int CPR = HID / 8;  // 16-B chunks per row
+  constexpr int KS = HID / 32;  // k-steps = 32-column blocks
+  constexpr int TROWS = 16 * L2F_MT;
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int net = blockIdx.y;
+  const int m = lane & 15, g = lane >> 4;
+  const bf16_t* __restrict__ W2 = net ? W2c : W2a;
+  const bf16_t* __restrict__ b2 = net ? b2c : b2a;
+  const long nbase = (long)net * S;
+  const int ntiles = S / TROWS;
+  const int stride = gridDim.x * L2F_WAVES;
+  int t = blockIdx.x * L2F_WAVES + wid;
+
+  bf16x8 x[L2F_MT][KS];
+  // always_inline: the lambda does not carry the kernel's target attribute,
+  // and a call that stays a call would put x in scratch
+  auto load_x = [&](int tile) __attribute__((always_inline)) {
+#pragma unroll
+    for (int mi = 0; mi < L2F_MT; ++mi) {
+      const bf16_t* xr =
+          H1 + (nbase + (long)tile * TROWS + mi * 16 + m) * HID + g * 8;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        x[mi][ks] = *reinterpret_cast<const bf16x8*>(xr + ks * 32);
+    }
+  };
+  // the first tile's rows are in flight while the weights are staged
+  if (t < ntiles) load_x(t);
+
+  for (int c = threadIdx.x; c < HID * CPR; c += L2F_WAVES * 64) {
+    const int rho = c / CPR, k8 = (c % CPR) * 8;
+    const int mm = rho & 15, step = rho >> 4;
+    const int n = (step >> 1) * 32 + (mm >> 2) * 8 + (step & 1) * 4 + (mm & 3);
+    *reinterpret_cast<bf16x8*>(&lds.W2[rho][k8]) =
+        *reinterpret_cast<const bf16x8*>(W2 + n * HID + k8);
+  }
+  for (int c = threadIdx.x; c < 16 * CPR; c += L2F_WAVES * 64) {
+    const int n = c / CPR, k8 = (c % CPR) * 8;
+    bf16x8 w = zero_bf16x8();
+    if (net == 0)
+      w = *reinterpret_cast<const bf16x8*>(Wh + n * HID + k8);
+    else if (n == 0)
+      w = *reinterpret_cast<const bf16x8*>(Wv + k8);
+    *reinterpret_cast<bf16x8*>(&lds.W[n][k8]) = w;
+  }
+  __syncthreads();  // the only barrier: every wave reaches it
+
+  const bool head = net == 0 || vpred != nullptr;
+  const float hb_raw = bf2f(net == 0 ? bh[m] : bv[0]);
+  const float hbias = (net == 0 || m == 0) ? hb_raw : 0.0f;
+
+  while (t < ntiles) {
+    const int row0 = t * TROWS;
+    f32x4 hacc[L2F_MT];
+#pragma unroll
+    for (int mi = 0; mi < L2F_MT; ++mi) hacc[mi] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int b = 0; b < KS; ++b) {
+      f32x4 acc[2][L2F_MT];
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int mi = 0; mi < L2F_MT; ++mi) acc[p][mi] = {0.f, 0.f, 0.f, 0.f};
+      const bf16_t* w0p = &lds.W2[b * 32 + m][g * 8];
+      const bf16_t* w1p = &lds.W2[b * 32 + 16 + m][g * 8];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(w0p + ks * 32);
+        const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(w1p + ks * 32);
+#pragma unroll
+        for (int mi = 0; mi < L2F_MT; ++mi) {
+          acc[0][mi] = MFMA_BF16_16x16x32(w0, x[mi][ks], acc[0][mi], 0, 0, 0);
+          acc[1][mi] = MFMA_BF16_16x16x32(w1, x[mi][ks], acc[1][mi], 0, 0, 0);
+        }
+      }
+      const int c0 = b * 32 + g * 8;
+      const bf16x8 bias = *reinterpret_cast<const bf16x8*>(b2 + c0);
+      const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&lds.W[m][c0]);
+#pragma unroll
+      for (int mi = 0; mi < L2F_MT; ++mi) {
+        bf16x8 zv, hv;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int j = p * 4 + r;
+            zv[j] = f2bf(acc[p][mi][r] + bf2f(bias[j]));
+            hv[j] = f2bf(silu_f(bf2f(zv[j])));
+          }
+        const long o = (nbase + row0 + mi * 16 + m) * HID + c0;
+        *reinterpret_cast<bf16x8*>(Z2 + o) = zv;
+        *reinterpret_cast<bf16x8*>(H2 + o) = hv;
+        if (head) hacc[mi] = MFMA_BF16_16x16x32(hv, wh, hacc[mi], 0, 0, 0);
+      }
+    }
+    if (head) {
+#pragma unroll
+      for (int mi = 0; mi < L2F_MT; ++mi) {
+        const int rbase = row0 + mi * 16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          lds.O[wid][g * 4 + r][m] = f2bf(hacc[mi][r] + hbias);
+        wave_lds_sync();
+        if (net == 0) {
+          if (lane < 32) {
+            const int row = lane >> 1, half = (lane & 1) * 8;
+            *reinterpret_cast<bf16x8*>(heads + (long)(rbase + row) * 16 + half) =
+                *reinterpret_cast<const bf16x8*>(&lds.O[wid][row][half]);
+          }
+        } else if (lane < 16) {
+          vpred[rbase + lane] = lds.O[wid][lane][0];
+        }
+        wave_lds_sync();
+      }
+    }
+    t += stride;
+    if (t < ntiles) load_x(t);
+  }
+}
+
+// Workgroups per net: one per CU of half the device, at most one per 8 wave
+// tiles. The attribute that admits more than 64 KB of dynamic LDS is set
+// once per instantiation.
+template <int HID>
+static int l2_fwd_heads_launch(const void* H1, const void* W2a, const void* b2a,
+                               const void* W2c, const void* b2c, const void* Wh,
+                               const void* bh, const void* Wv, const void* bv,
+                               void* Z2, void* H2, void* heads, void* vpred,
+                               int S, hipStream_t s) {
+  constexpr int LDS_BYTES = (int)sizeof(L2FwdLds<HID>);
+  auto kernel = l2_fwd_heads_kernel<HID>;
+  static const bool fits =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                          LDS_BYTES) == hipSuccess;
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
+            hipSuccess)
+      n = 0;
+    return n;
+  }();
+  if (!fits) {
+    (void)hipGetLastError();
+    return 1;
+  }
+  const int want = (S / (16 * L2F_MT) + L2F_WAVES - 1) / L2F_WAVES;
+  const int cap = cus / 2 > 0 ? cus / 2 : 1;
+  dim3 grid(want < cap ? want : cap, 2), block(L2F_WAVES * 64);
+  hipLaunchKernelGGL(kernel, grid, block, LDS_BYTES, s, (const bf16_t*)H1,
+                     (const bf16_t*)W2a, (const bf16_t*)b2a,
+                     (const bf16_t*)W2c, (const bf16_t*)b2c, (const bf16_t*)Wh,
+                     (const bf16_t*)bh, (const bf16_t*)Wv, (const bf16_t*)bv,
+                     (bf16_t*)Z2, (bf16_t*)H2, (bf16_t*)heads, (bf16_t*)vpred,
+                     S);
+  return 0;
+}
+
+// Returns 0 after the launch, 1 for a shape the kernel does not take: S not
+// a multiple of 128, or a width whose W2 does not fit in LDS (HID 512).
+extern "C" int launch_l2_fwd_heads(const void* H1, const void* W2a,
+                                   const void* b2a, const void* W2c,
+                                   const void* b2c, const void* Wh,
+                                   const void* bh, const void* Wv,
+                                   const void* bv, void* Z2, void* H2,
+                                   void* heads, void* vpred, int S, int HID,
+                                   void* stream) {
+  if (S <= 0 || S % 128 != 0) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (HID == 128)
+    return l2_fwd_heads_launch<128>(H1, W2a, b2a, W2c, b2c, Wh, bh, Wv, bv, Z2,
+                                    H2, heads, vpred, S, s);
+  if (HID == 256)
+    return l2_fwd_heads_launch<256>(H1, W2a, b2a, W2c, b2c, Wh, bh, Wv, bv, Z2,
+                                    H2, heads, vpred, S, s);
+  return 1;
 }
 
 // Fused minibatch gather: one kernel replaces 6 index_selects. Gathers the

@@ -18,10 +18,13 @@ stoix_amd/ops/csrc/mlp.hip:
                  minibatch)
   minibatch:     layer-1 fused linear_silu_pair, both nets in
                  one launch over the shared Xmb (custom MFMA wins at K=32,
-                 row-contiguous stores) -> layer-2 tuned hipBLASLt GemmAndBias
-                 per net (library wins at K=256) -> silu_heads_fwd (ONE
-                 stacked silu that also forms both heads from the tile it
-                 holds) -> ppo_head_loss (per-row losses + analytic
+                 row-contiguous stores) -> linear_silu_heads_pair (layer 2
+                 of both nets, its silu and the heads in ONE launch: W2 held
+                 in LDS, Z2 written once and not read back;
+                 STOIX_FUSED_L2=0, H=512 or S % 128 != 0: tuned hipBLASLt
+                 GemmAndBias per net -> silu_heads_fwd, ONE stacked silu
+                 that also forms both heads from the tile it holds; same
+                 bits) -> ppo_head_loss (per-row losses + analytic
                  head bwd; metrics only on the reported minibatch)
                  -> stacked backward over [2, S, H] buffers: heads_bwd_silu
                  (head dgrads formed inside the layer-2 silu backward),
@@ -406,6 +409,15 @@ class FusedPPOEngine:
         # bit. Where the two-launch form applies: _tail_eligible.
         self.fused_tail = _os.environ.get("STOIX_FUSED_TAIL", "1") != "0"
         self.no_vpred = z(0)
+        # STOIX_FUSED_L2: 1 (default) = the layer-2 forward of both nets, the
+        # SiLU and the heads in one launch with W2 held in LDS
+        # (linear_silu_heads_pair) in place of two hipBLASLt GEMMs and
+        # silu_heads_fwd; Z2 is written once and not read back. 0 = those
+        # three launches. Same Z2, H2 and heads bit for bit
+        # (profiles/l2_fwd_SUMMARY.md). Needs the fused heads; where the
+        # launcher does not take the shape (H = 512, S % 128 != 0) the three
+        # launches run.
+        self.fused_l2 = _os.environ.get("STOIX_FUSED_L2", "1") != "0"
         # side-stream gather prefetch. Measured SLOWER (28.0 vs 26.8
         # ms/step): the backward kernels already fill all 256 CUs, so the
         # concurrent gather steals bandwidth instead of hiding latency.
@@ -723,12 +735,21 @@ class FusedPPOEngine:
                 gather_into(mb, w)
             # ---- forward. Layer 1 (K=32): the custom fused Linear+SiLU
             # MFMA kernel wins (14.4 us vs 11.2 GEMM + silu pass). Layer 2
-            # (K=256): hipBLASLt's tuned GemmAndBias (14.4 us) beats the
-            # custom kernel (24.6 us), so run both nets' GEMMs then ONE
-            # silu over the stacked [2, S, H] preacts.
+            # (K=256): one launch for both nets' GEMM, silu and heads with
+            # W2 in LDS and Z2 not read back (STOIX_FUSED_L2). Knob off, or
+            # a shape the launcher does not take: hipBLASLt's tuned
+            # GemmAndBias per net (14.4 us against 24.6 for linear_silu,
+            # which re-reads W from L2 per tile), then ONE silu over the
+            # stacked [2, S, H] preacts.
             self.layer1_forward(w.Xmb)
-            torch.addmm(a16["b2"], self.H1[0], a16["W2"].t(), out=self.Z2[0])
-            torch.addmm(c16["b2"], self.H1[1], c16["W2"].t(), out=self.Z2[1])
+            vp = self.vpred if self.fused_vpred else self.no_vpred
+            l2 = self.fused_l2 and self.fused_heads and ext.linear_silu_heads_pair(
+                self.H1, a16["W2"], a16["b2"], c16["W2"], c16["b2"],
+                a16["Wh"], a16["bh"], c16["Wv"], c16["bv"],
+                self.Z2, self.H2, self.heads, vp)
+            if not l2:
+                torch.addmm(a16["b2"], self.H1[0], a16["W2"].t(), out=self.Z2[0])
+                torch.addmm(c16["b2"], self.H1[1], c16["W2"].t(), out=self.Z2[1])
             # ---- silu + the actor head in one pass over Z2 (the N=16 head
             # GEMM is a re-read of H2[0]); the N=1 value head stays a
             # hipBLASLt GEMM unless the knob asks for it too (see
@@ -736,10 +757,10 @@ class FusedPPOEngine:
             # head-backward kernel. Knob off: silu, then both heads as
             # hipBLASLt GEMMs.
             if self.fused_heads:
-                ext.silu_heads_fwd(
-                    self.Z2, a16["Wh"], a16["bh"], c16["Wv"], c16["bv"],
-                    self.H2, self.heads,
-                    self.vpred if self.fused_vpred else self.no_vpred)
+                if not l2:
+                    ext.silu_heads_fwd(
+                        self.Z2, a16["Wh"], a16["bh"], c16["Wv"], c16["bv"],
+                        self.H2, self.heads, vp)
                 if not self.fused_vpred:
                     torch.addmm(c16["bv"], self.H2[1],
                                 c16["Wv"].view(self.H, 1), out=self.vpred)

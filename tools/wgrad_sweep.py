@@ -191,5 +191,53 @@ def main_pair():
     print(f"reduce: two slab_reduce {t2:.2f} us, slab_reduce_pair {tp:.2f} us")
 
 
+def main_l2fwd():
+    """--l2fwd: the layer-2 forward group at the flagship shape, the fused
+    launch (ext.linear_silu_heads_pair) against the two addmm calls and
+    silu_heads_fwd it replaces, with and without the value head. Four operand
+    sets (about 400 MB) rotate so that the rows come from HBM."""
+    import math
+
+    ext = ops.ext(required=True)
+    dev, bf, H, NSET = torch.device("cuda:0"), torch.bfloat16, 256, 4
+    r = lambda *s: torch.randn(*s, device=dev)
+    W2 = (r(2, H, H) / math.sqrt(H)).to(bf)
+    b2, Wh, bh = (0.5 * r(2, H)).to(bf), (r(16, H) / math.sqrt(H)).to(bf), r(16).to(bf)
+    Wv, bv = (r(H) / math.sqrt(H)).to(bf), r(1).to(bf)
+    sets = [dict(H1=r(2, S, H).to(bf), Z2=torch.empty(2, S, H, device=dev, dtype=bf),
+                 H2=torch.empty(2, S, H, device=dev, dtype=bf),
+                 heads=torch.empty(S, 16, device=dev, dtype=bf),
+                 vpred=torch.empty(S, 1, device=dev, dtype=bf)) for _ in range(NSET)]
+    none = torch.empty(0, device=dev, dtype=bf)
+    it = [0]
+
+    def old(vp):
+        b = sets[it[0] % NSET]
+        it[0] += 1
+        torch.addmm(b2[0], b["H1"][0], W2[0].t(), out=b["Z2"][0])
+        torch.addmm(b2[1], b["H1"][1], W2[1].t(), out=b["Z2"][1])
+        ext.silu_heads_fwd(b["Z2"], Wh, bh, Wv, bv, b["H2"], b["heads"],
+                           b["vpred"] if vp else none)
+
+    def new(vp):
+        b = sets[it[0] % NSET]
+        it[0] += 1
+        assert ext.linear_silu_heads_pair(
+            b["H1"], W2[0], b2[0], W2[1], b2[1], Wh, bh, Wv, bv, b["Z2"],
+            b["H2"], b["heads"], b["vpred"] if vp else none)
+
+    need = 3 * 2 * S * H * 2 + S * 32  # H1 in, Z2 and H2 out, heads out
+    for vp in (False, True):
+        t_old, t_new = timeit(lambda: old(vp)), timeit(lambda: new(vp))
+        print(f"l2fwd S={S} H={H} vpred={vp}: 2 addmm + silu_heads_fwd "
+              f"{t_old:.2f} us; linear_silu_heads_pair {t_new:.2f} us "
+              f"({need / t_new / 1e6:.2f} TB/s of the {need / 1e6:.1f} MB needed)")
+
+
 if __name__ == "__main__":
-    main_pair() if "--pair" in sys.argv[1:] else main()
+    if "--l2fwd" in sys.argv[1:]:
+        main_l2fwd()
+    elif "--pair" in sys.argv[1:]:
+        main_pair()
+    else:
+        main()
