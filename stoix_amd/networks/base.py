@@ -17,7 +17,11 @@ Tensor = torch.Tensor
 
 
 class FeedForwardActor(nn.Module):
-    """input-embed -> torso -> action head (returns a Distribution)."""
+    """input-embed -> torso -> action head (returns a Distribution).
+
+    An fp32 MLP actor with a tanh-normal head on the GPU runs as one launch
+    forward and one input-gradient launch backward (ops/actor_mlp.py,
+    ``STOIX_FUSED_ACTOR``); anything else runs its modules one by one."""
 
     def __init__(self, torso: nn.Module, action_head: nn.Module, input_layer: Optional[nn.Module] = None):
         super().__init__()
@@ -26,6 +30,10 @@ class FeedForwardActor(nn.Module):
         self.action_head = action_head
 
     def forward(self, obs: Any):
+        from stoix_amd.ops.actor_mlp import actor_forward, actor_route_to_kernel
+
+        if actor_route_to_kernel(self, obs):
+            return actor_forward(self, obs)
         x = self.input_layer(obs) if self.input_layer is not None else obs
         return self.action_head(self.torso(x))
 

@@ -58,9 +58,10 @@ def _headers_digest() -> str:
 # is a pragma inside the files that need it off, not a flag here.)
 # tanh_normal.hip (the SAC sampling and loss chain) likewise, and qens.hip
 # (the fp32 MFMA layers of the Q-ensemble critics), and multi_adam.hip (the
-# multi-tensor clip + Adam + polyak tail of the replay learners).
+# multi-tensor clip + Adam + polyak tail of the replay learners), and
+# actor_mlp.hip (the fp32 MFMA Gaussian actor, forward and input gradients).
 OWN_OBJECT_SOURCES = [CSRC / "noisy.hip", CSRC / "qr.hip", CSRC / "tanh_normal.hip",
-                      CSRC / "qens.hip", CSRC / "multi_adam.hip"]
+                      CSRC / "qens.hip", CSRC / "multi_adam.hip", CSRC / "actor_mlp.hip"]
 OWN_OBJECT_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc",
                     "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 

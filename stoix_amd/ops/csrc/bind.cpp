@@ -1572,6 +1572,145 @@ bool qens_linear_wgrad(torch::Tensor dH, torch::Tensor aux, torch::Tensor X0,
              (int)N, (int)E, (int)act, cur_stream()) == 0;
 }
 
+// The Gaussian actor MLP (actor_mlp.hip). The net's tensors as a by-value
+// ActorNet; false: ineligible (a dtype, a layer count or a width the kernels
+// do not take). Wrong devices, shapes that disagree with each other and
+// non-contiguous tensors are errors.
+bool actor_net(const torch::Tensor& X_like, int64_t K0,
+               const std::vector<torch::Tensor>& W,
+               const std::vector<torch::Tensor>& b, const torch::Tensor& Wloc,
+               const torch::Tensor& bloc, const torch::Tensor& Wscale,
+               const torch::Tensor& bscale, ActorNet* net) {
+  const size_t L = W.size();
+  if (L < 1 || L > ACTOR_MAX_L || b.size() != L) return false;
+  const int64_t S = X_like.size(0);
+  if (S < 1 || S > (1LL << 30) || K0 < 1) return false;
+  int64_t K = K0;
+  for (size_t l = 0; l < ACTOR_MAX_L; ++l) {
+    net->W[l] = net->b[l] = nullptr;
+    net->N[l] = 0;
+  }
+  for (size_t l = 0; l < L; ++l) {
+    if (!qens_f32(W[l], "W") || !qens_f32(b[l], "b")) return false;
+    TORCH_CHECK(W[l].dim() == 2 && W[l].size(1) == K && b[l].dim() == 1 &&
+                    b[l].size(0) == W[l].size(0),
+                "layer ", l, ": W must be [N, ", K, "] and b [N]");
+    const int64_t N = W[l].size(0);
+    if (N < 16 || N > 256 || N % 16 != 0) return false;
+    net->W[l] = W[l].data_ptr<float>();
+    net->b[l] = b[l].data_ptr<float>();
+    net->N[l] = (int)N;
+    K = N;
+  }
+  if (!qens_f32(Wloc, "Wloc") || !qens_f32(bloc, "bloc") ||
+      !qens_f32(Wscale, "Wscale") || !qens_f32(bscale, "bscale"))
+    return false;
+  TORCH_CHECK(Wloc.dim() == 2 && Wloc.size(1) == K &&
+                  Wscale.sizes() == Wloc.sizes() && bloc.dim() == 1 &&
+                  bloc.size(0) == Wloc.size(0) &&
+                  bscale.sizes() == bloc.sizes(),
+              "the head must be two [A, ", K, "] linears with [A] biases");
+  const int64_t A = Wloc.size(0);
+  if (A < 1 || A > 64) return false;
+  net->Wloc = Wloc.data_ptr<float>();
+  net->bloc = bloc.data_ptr<float>();
+  net->Wscale = Wscale.data_ptr<float>();
+  net->bscale = bscale.data_ptr<float>();
+  net->L = (int)L;
+  net->K0 = (int)K0;
+  net->A = (int)A;
+  net->S = (int)S;
+  return true;
+}
+
+// One [S, N[l]] buffer per hidden layer, or an empty list (all absent).
+void actor_bufs(const std::vector<torch::Tensor>& ts, const char* name,
+                const ActorNet& net, ActorBufs* out) {
+  for (int l = 0; l < ACTOR_MAX_L; ++l) out->p[l] = nullptr;
+  if (ts.empty()) return;
+  TORCH_CHECK((int)ts.size() == net.L, name, ": one tensor per hidden layer");
+  for (int l = 0; l < net.L; ++l) {
+    TORCH_CHECK(ts[l].is_cuda() && ts[l].is_contiguous() &&
+                    ts[l].scalar_type() == torch::kFloat32 &&
+                    ts[l].dim() == 2 && ts[l].size(0) == net.S &&
+                    ts[l].size(1) == net.N[l],
+                name, "[", l, "] must be contiguous fp32 [", net.S, ", ",
+                net.N[l], "]");
+    out->p[l] = ts[l].data_ptr<float>();
+  }
+}
+
+void check_actor_rows(const torch::Tensor& t, const char* name,
+                      const ActorNet& net) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32 && t.dim() == 2 &&
+                  t.size(0) == net.S && t.size(1) == net.A,
+              name, " must be contiguous fp32 [", net.S, ", ", net.A, "]");
+}
+
+// The whole actor in one launch: loc and scale [S, A]; with a backward to
+// follow also spre [S, A], H[l] and (SiLU) Z[l] [S, N_l], else empty / empty
+// lists. False: ineligible, nothing launched.
+bool actor_mlp_fwd(torch::Tensor X, std::vector<torch::Tensor> W,
+                   std::vector<torch::Tensor> b, torch::Tensor Wloc,
+                   torch::Tensor bloc, torch::Tensor Wscale,
+                   torch::Tensor bscale, double min_scale, int64_t act,
+                   torch::Tensor loc, torch::Tensor scale, torch::Tensor spre,
+                   std::vector<torch::Tensor> H, std::vector<torch::Tensor> Z) {
+  TORCH_CHECK(X.dim() == 2, "X must be [S, K0]");
+  ActorNet net;
+  if (!qens_f32(X, "X") ||
+      !actor_net(X, X.size(1), W, b, Wloc, bloc, Wscale, bscale, &net))
+    return false;
+  check_actor_rows(loc, "loc", net);
+  check_actor_rows(scale, "scale", net);
+  float* sp = nullptr;
+  if (spre.numel() > 0) {
+    check_actor_rows(spre, "spre", net);
+    sp = spre.data_ptr<float>();
+  }
+  ActorBufs Hp, Zp;
+  actor_bufs(H, "H", net, &Hp);
+  actor_bufs(Z, "Z", net, &Zp);
+  return launch_actor_mlp_fwd(X.data_ptr<float>(), net, (float)min_scale,
+                              (int)act, loc.data_ptr<float>(),
+                              scale.data_ptr<float>(), sp, Hp, Zp,
+                              cur_stream()) == 0;
+}
+
+// The whole input-gradient chain in one launch: dZ[l] [S, N_l] of every hidden
+// layer and dZh [2, S, A] = (dloc, dscale * softplus'(spre)). aux[l] is the
+// saved H (ReLU) or Z (SiLU). W[0] is not read (there is no dX).
+bool actor_mlp_dgrad(torch::Tensor dloc, torch::Tensor dscale,
+                     torch::Tensor spre, int64_t K0,
+                     std::vector<torch::Tensor> W, std::vector<torch::Tensor> b,
+                     torch::Tensor Wloc, torch::Tensor bloc,
+                     torch::Tensor Wscale, torch::Tensor bscale, int64_t act,
+                     std::vector<torch::Tensor> aux,
+                     std::vector<torch::Tensor> dZ, torch::Tensor dZh) {
+  TORCH_CHECK(dloc.dim() == 2, "dloc must be [S, A]");
+  ActorNet net;
+  if (!qens_f32(dloc, "dloc") ||
+      !actor_net(dloc, K0, W, b, Wloc, bloc, Wscale, bscale, &net))
+    return false;
+  check_actor_rows(dloc, "dloc", net);
+  check_actor_rows(dscale, "dscale", net);
+  check_actor_rows(spre, "spre", net);
+  TORCH_CHECK(dZh.is_cuda() && dZh.is_contiguous() &&
+                  dZh.scalar_type() == torch::kFloat32 && dZh.dim() == 3 &&
+                  dZh.size(0) == 2 && dZh.size(1) == net.S &&
+                  dZh.size(2) == net.A,
+              "dZh must be contiguous fp32 [2, S, A]");
+  TORCH_CHECK(!aux.empty() && !dZ.empty(), "aux and dZ: one per hidden layer");
+  ActorBufs ax, dz;
+  actor_bufs(aux, "aux", net, &ax);
+  actor_bufs(dZ, "dZ", net, &dz);
+  return launch_actor_mlp_dgrad(dloc.data_ptr<float>(),
+                                dscale.data_ptr<float>(),
+                                spre.data_ptr<float>(), net, (int)act, ax, dz,
+                                dZh.data_ptr<float>(), cur_stream()) == 0;
+}
+
 // The by-value table of the multi-tensor optimiser tail (multi_adam.hip),
 // built from the tensors torch's Adam owns: pointer reads only, no device
 // sync and nothing copied to the device. Tensor i belongs to chain
@@ -2037,6 +2176,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Q-ensemble input gradient, per member or summed over members");
   m.def("qens_linear_wgrad", &qens_linear_wgrad,
         "Q-ensemble weight and bias gradients (split-S + reduce)");
+  m.def("actor_mlp_fwd", &actor_mlp_fwd,
+        "Gaussian actor MLP forward, every layer and the head in one launch "
+        "(fp32)");
+  m.def("actor_mlp_dgrad", &actor_mlp_dgrad,
+        "Gaussian actor MLP input-gradient chain in one launch: dZ of every "
+        "layer and of the head");
   m.def("multi_adam_norm", &multi_adam_norm,
         "optimiser tail, launch A: ordered grad-norm partials and step + 1 "
         "for up to 4 chains of torch-owned tensors");

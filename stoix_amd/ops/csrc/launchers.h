@@ -66,6 +66,22 @@ struct QensOut {
   float* p[QENS_MAX_E];
 };
 
+// The Gaussian actor MLP (actor_mlp.hip): 1..ACTOR_MAX_L hidden nn.Linear
+// layers and the two head linears, all read in place, passed by value.
+// Entries past L are not read.
+#define ACTOR_MAX_L 4
+struct ActorNet {
+  const float* W[ACTOR_MAX_L];  // [N[l], N[l-1]] (layer 0: [N[0], K0])
+  const float* b[ACTOR_MAX_L];  // [N[l]]
+  int N[ACTOR_MAX_L];
+  const float *Wloc, *bloc, *Wscale, *bscale;  // [A, N[L-1]], [A]
+  int L, K0, A, S;
+};
+// One [S, N[l]] fp32 buffer per hidden layer (saved H / Z, dZ); null: absent.
+struct ActorBufs {
+  float* p[ACTOR_MAX_L];
+};
+
 // The multi-tensor optimiser tail (multi_adam.hip): every tensor of up to
 // MADAM_MAX_CHAINS clip + Adam (+ polyak) chains, passed to both kernels by
 // value. A chain's tensors are adjacent, in chain order; tensor i owns the
@@ -444,5 +460,23 @@ int launch_qens_linear_wgrad(const float* dH, const float* AUX,
                              float* slab, const QensOut& dW, const QensOut& dB,
                              int S, int K0, int K1, int N, int E, int act,
                              void* stream);
+
+// ---- actor_mlp.hip. fp32 throughout. act: 1 SiLU, 2 ReLU. Eligible: 1..4
+// hidden layers, each width a multiple of 16 and at most 256, K0 >= 1,
+// 1 <= A <= 64, S >= 1, 16-byte aligned H / Z / dZ buffers. Both return 0
+// after the launch, 1 for anything else, launching nothing.
+// loc / scale [S, A]; spre [S, A] (the scale's pre-softplus value) and
+// H.p[l] / Z.p[l] [S, N[l]] may be null: not stored (Z is stored for SiLU
+// only).
+int launch_actor_mlp_fwd(const float* X, const ActorNet& net, float min_scale,
+                         int act, float* loc, float* scale, float* spre,
+                         const ActorBufs& H, const ActorBufs& Z, void* stream);
+// aux.p[l]: the saved H (ReLU) or Z (SiLU) of layer l. Writes dZ.p[l]
+// [S, N[l]] for every hidden layer and dZh [2, S, A] = (dloc, dscale *
+// softplus'(spre)).
+int launch_actor_mlp_dgrad(const float* dloc, const float* dscale,
+                           const float* spre, const ActorNet& net, int act,
+                           const ActorBufs& aux, const ActorBufs& dZ,
+                           float* dZh, void* stream);
 
 }  // extern "C"
